@@ -12,7 +12,11 @@ partitions, using the reference's experiment tables
     N=8  U-Net pipeline-8  B=640, chunks=40, balance [16, 27, 31, 44, 22, 57, 27, 17]
 
 The top-level ``value`` is the U-Net headline: the reference balance on the plain eager
-engine.  After it, every run also times (``--sections``), in this order:
+engine.  A plain run times the headline alone and prints one JSON record; with
+``--dump-outputs DIR`` it also writes what the last timed step computed (``loss``, the
+gradients and the updated parameters; weights and inputs are seeded, so two builds can be
+compared array for array).  With ``--full`` the run also times (``--sections``), in this
+order:
 
 * ``baseline``: the reference's speed-up denominator, U-Net(5,64) *without* GPipe
   (plain model, B=40, no checkpointing) on rank 0's GPU, so ``speedup_vs_baseline``
@@ -33,12 +37,13 @@ engine.  After it, every run also times (``--sections``), in this order:
 
 One process per GPU (``torch.distributed.run``), RCCL point-to-point between
 stages; fp32 like the reference.  Rank 0 prints the JSON record right after the headline
-and re-prints it, augmented, after every section (each line complete; the last one the
-most complete), so a late section that fails cannot lose the headline.
+and, with ``--full``, re-prints it, augmented, after every section (each line complete; the
+last one the most complete), so a late section that fails cannot lose the headline.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
-        bench.py --gpus 8
+        bench.py --gpus 8 --full
 """
 import argparse
 import datetime
@@ -122,6 +127,8 @@ RESNET_EXPERIMENTS = {
 }
 # the reference's ResNet speed-up denominator: ResNet-101 without GPipe, one GPU
 RESNET_BASELINE = dict(name='baseline', batch=118, ref=95.862)
+# --dump-outputs: most elements of one dumped array (float32: 16 MiB; a rank writes two)
+DUMP_ELEMENTS = 4 << 20
 
 
 def parse() -> argparse.Namespace:
@@ -129,6 +136,17 @@ def parse() -> argparse.Namespace:
     p.add_argument('--gpus', type=int, default=int(os.environ.get('WORLD_SIZE', '1')))
     p.add_argument('--steps', type=int, default=5)
     p.add_argument('--warmup', type=int, default=2)
+    p.add_argument('--full', action='store_true',
+                   help='after the headline, also run everything else this script measures: '
+                        'the extra sections (--sections), the tuned balances (--also-tuned), '
+                        'the receive-wait probe (--probe) and --profile-steps.  Without it '
+                        'the run times the headline alone and prints one JSON record')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed headline step '
+                        'computed as DIR/<name>.npy (float32): loss (last stage), grads and '
+                        'params (each rank\'s gradients and updated parameters, flattened; '
+                        'a fixed seeded sample of 4M elements when larger; '
+                        'suffixed _rank<r> at N > 1)')
     p.add_argument('--model', choices=['unet', 'amoebanet', 'resnet'], default='unet')
     p.add_argument('--checkpoint', choices=['always', 'except_last', 'never'], default=None,
                    help='override the experiment checkpoint mode (default: reference mode)')
@@ -142,7 +160,8 @@ def parse() -> argparse.Namespace:
                    help="after the headline timing, time the MI355X-tuned balance too and "
                         "report it as the 'tuned' field (auto: when N > 1 and it differs)")
     p.add_argument('--sections', default='auto',
-                   help="comma-separated extra timings after the headline, in this order: "
+                   help="with --full: comma-separated extra timings after the headline, in this "
+                        "order: "
                         "'baseline' (U-Net without GPipe, B=40, rank 0), 'gpipe' (N=1: the "
                         "headline through single-process GPipe), 'amoebanet' (AmoebaNet-D "
                         "n{N}m32 and, at N=2, n2m1), 'resnet' (ResNet-101 pipeline-{N} and its "
@@ -195,7 +214,20 @@ def parse() -> argparse.Namespace:
                    help='smallest striped message, MB')
     p.add_argument('--profile-steps', type=int, default=0,
                    help='after timing, run N more steps under torch.profiler (rank 0)')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0 or (args.section_steps or 1) < 1:
+        p.error('--steps and --section-steps must be at least 1 and --warmup at least 0')
+    if not args.full:
+        asked = [flag for flag, given in (
+            ('--sections', args.sections not in ('auto', 'none')),
+            ('--section-steps', args.section_steps is not None),
+            ('--also-tuned yes', args.also_tuned == 'yes'),
+            ('--probe on', args.probe == 'on'),
+            ('--profile-steps', args.profile_steps > 0)) if given]
+        if asked:
+            p.error(f"{', '.join(asked)}: only with --full (a plain run times the headline "
+                    'alone)')
+    return args
 
 
 def even_balance(layers: int, parts: int) -> list:
@@ -294,9 +326,11 @@ class Bench:
     # -- timing -----------------------------------------------------------------------------
 
     def timed(self, step: Callable[[], None], steps: int, warmup: int, tag: str,
-              settle: Optional[Callable[[], bool]] = None) -> Dict[str, float]:
+              settle: Optional[Callable[[], bool]] = None,
+              before_last: Optional[Callable[[], None]] = None) -> Dict[str, float]:
         """``warmup`` untimed steps (plus any until ``settle()``), then ``steps`` timed steps
-        bracketed by a barrier and a device sync; elapsed = MAX over ranks."""
+        bracketed by a barrier and a device sync; elapsed = MAX over ranks.
+        ``before_last()`` is called ahead of the last timed step (--dump-outputs)."""
         t0 = time.time()
         first_s = 0.0
         for k in range(warmup):
@@ -311,8 +345,11 @@ class Bench:
         warm_s = time.time() - t0
         self.sync()
         start = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        if before_last is not None:
+            before_last()
+        step()
         self.sync()
         elapsed = time.perf_counter() - start
         if self.world > 1:
@@ -324,8 +361,10 @@ class Bench:
 
     def pipeline(self, kind: str, exp: Dict[str, Any], balance: List[int], checkpoint: str,
                  steps: int, tag: str, probe: bool = False, stripes: Optional[bool] = None,
-                 graph_cells: Optional[bool] = None) -> Dict[str, Any]:
-        """Build the PipelineStage for ``balance``, warm up, time ``steps`` SGD steps."""
+                 graph_cells: Optional[bool] = None,
+                 dump: Optional[str] = None) -> Dict[str, Any]:
+        """Build the PipelineStage for ``balance``, warm up, time ``steps`` SGD steps.
+        ``dump``: directory for the last timed step's outputs (--dump-outputs)."""
         from torchgpipe_amd.parallel import PipelineStage
         from torchgpipe_amd.parallel.stage import signature_of
         args = self.args
@@ -364,6 +403,9 @@ class Bench:
         # run their RCCL relay chains
         if stripes is None:
             stripes = choice(args.stripes, False)
+        # the same weights (initialised on the device as each partition materialises) and,
+        # in data(), the same inputs in every run with the same arguments
+        torch.manual_seed(0)
         stage = PipelineStage(self.build(kind), balance, device=self.device, chunks=chunks,
                               checkpoint=checkpoint, timeout=args.timeout,
                               overlap_recompute=overlap, overlap_forward=overlap_fwd,
@@ -382,11 +424,21 @@ class Bench:
         x, target, loss_fn, shape = self.data(kind, batch, stage.is_first, stage.is_last)
         signature = signature_of(torch.empty(batch, *shape, device='meta'))
 
+        # --dump-outputs: what the last timed step hands its caller (armed before that step)
+        kept: Dict[str, Any] = {}
+        keep = False
+
         def step() -> None:
-            stage.train_step(x, target, loss_fn, signature=signature)
+            loss = stage.train_step(x, target, loss_fn, signature=signature)
+            if keep:
+                kept.update(loss=loss, grads=[p.grad for p in params])
             if optimizer is not None:
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=True)
+
+        def arm() -> None:
+            nonlocal keep
+            keep = True
 
         if self.gpu:
             torch.cuda.reset_peak_memory_stats(self.device)
@@ -395,7 +447,11 @@ class Bench:
             settle = lambda: stage._segments is not None and stage._segments.captured  # noqa: E731
         elif stripes:  # the step that plans the stripes (and opens relay links) is untimed
             settle = lambda: stage.stripes_ready  # noqa: E731
-        res: Dict[str, Any] = self.timed(step, steps, args.warmup, tag, settle=settle)
+        res: Dict[str, Any] = self.timed(step, steps, args.warmup, tag, settle=settle,
+                                         before_last=arm if dump else None)
+        if dump:
+            keep = False
+            self.dump_outputs(dump, kept.pop('loss'), kept.pop('grads'), params)
         res.update(batch=batch, chunks=chunks, balance=list(balance), checkpoint=checkpoint,
                    steps=steps, overlap_recompute=overlap, cell_streams=int(cell_streams),
                    overlap_forward=overlap_fwd, graph_cells=graph_cells,
@@ -458,6 +514,45 @@ class Bench:
         del model, optimizer, x, target, step
         self.release()
         return res
+
+    def dump_outputs(self, directory: str, loss: Optional[torch.Tensor],
+                     grads: List[Optional[torch.Tensor]], params: List[torch.Tensor]) -> None:
+        """--dump-outputs: this rank's results of the last timed step as float32 ``.npy``
+        files -- ``loss`` (last stage), ``grads`` (what ``train_step`` left in ``p.grad``) and
+        ``params`` (after the optimizer step), each flattened over the parameters in order.
+        More than ``DUMP_ELEMENTS`` elements (over all ranks) are cut to a fixed seeded sample
+        of positions, the same positions in ``grads`` and ``params`` and in every run."""
+        import numpy as np
+        os.makedirs(directory, exist_ok=True)
+        suffix = f'_rank{self.rank}' if self.world > 1 else ''
+
+        def save(name: str, t: torch.Tensor) -> None:
+            np.save(os.path.join(directory, f'{name}{suffix}.npy'),
+                    t.detach().to('cpu', torch.float32).numpy())
+
+        if self.gpu:
+            torch.cuda.synchronize(self.device)
+        if loss is not None:
+            save('loss', loss)
+        if not params:
+            return
+        total = sum(p.numel() for p in params)
+        index = None
+        limit = DUMP_ELEMENTS // self.world  # (the ranks share the budget)
+        if total > limit:
+            # (drawn with replacement: a permutation of a 10^8-element model takes seconds)
+            picks = np.random.RandomState(0).randint(0, total, size=limit, dtype=np.int64)
+            index = torch.from_numpy(np.sort(picks)).to(self.device)
+
+        def flat(tensors: List[Optional[torch.Tensor]]) -> torch.Tensor:
+            whole = torch.cat([(torch.zeros_like(p) if t is None else t).reshape(-1).float()
+                               for t, p in zip(tensors, params)])
+            return whole if index is None else whole[index]
+
+        with torch.no_grad():
+            save('grads', flat(grads))
+            save('params', flat(list(params)))
+        self.log(f'outputs of the last timed step written to {directory}')
 
     def release(self) -> None:
         """Free what a finished timing held before the next one is built: autograd graphs
@@ -562,7 +657,7 @@ def main() -> None:
     elif args.balance != 'ref':
         exp['balance'] = [int(v) for v in args.balance.split(',')]
     batch, chunks, balance = exp['batch'], exp['chunks'], list(exp['balance'])
-    probe = choice(args.probe, world > 1)
+    probe = args.full and choice(args.probe, world > 1)
 
     # wall seconds of every timed section (warm-up, capture and diagnostics included), so a
     # multi-GPU run's budget can be checked section by section
@@ -588,7 +683,8 @@ def main() -> None:
 
     # 1. the headline: the reference balance on the plain eager engine (no multi-path
     #    transfers, no captured cells at N > 1 -- those have their own sections below)
-    main_run = b.pipeline(kind, exp, balance, checkpoint, args.steps, 'headline', probe=probe)
+    main_run = b.pipeline(kind, exp, balance, checkpoint, args.steps, 'headline', probe=probe,
+                          dump=args.dump_outputs)
     lap('headline')
     elapsed = main_run['elapsed']
     samples_per_s = batch * args.steps / elapsed
@@ -640,7 +736,9 @@ def main() -> None:
         record['per_rank'] = main_run['per_rank']
     emit()
 
-    if args.sections == 'auto':
+    if not args.full:
+        sections = set()
+    elif args.sections == 'auto':
         sections = set()
         if kind == 'unet':
             sections = {'baseline', 'amoebanet'}
@@ -758,8 +856,9 @@ def main() -> None:
             lap(name)
             emit()
 
-    also = args.also_tuned == 'yes' or (args.also_tuned == 'auto' and world > 1
-                                         and args.balance == 'ref' and tuned_balance != balance)
+    also = args.full and (args.also_tuned == 'yes'
+                          or (args.also_tuned == 'auto' and world > 1
+                              and args.balance == 'ref' and tuned_balance != balance))
 
     def tuned_section() -> None:
         t = b.pipeline(kind, exp, tuned_balance, checkpoint, extra_steps, 'tuned')

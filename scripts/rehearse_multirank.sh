@@ -12,7 +12,7 @@ for n in "$@"; do
     if [ "$model" = unet ]; then extra="--batch $((16 * n)) --chunks $((2 * n))"; else extra="--batch $((8 * n)) --chunks $((2 * n))"; fi
     timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" \
       --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus "$n" --steps 2 --warmup 1 \
-      --backend gloo --model "$model" $extra \
+      --backend gloo --model "$model" $extra --full \
       > "gpurun_out/rehearsal/${model}_n${n}.json" 2> "gpurun_out/rehearsal/${model}_n${n}.err"
     echo "n=$n $model ok: $(cut -c1-160 gpurun_out/rehearsal/${model}_n${n}.json)"
   done

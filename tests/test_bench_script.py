@@ -1,7 +1,8 @@
 """The bench.py driver contract: JSON records from rank 0, MAX-over-ranks timing.
 
-Rank 0 prints the complete record right after the headline and re-prints it, augmented,
-after every section; every line is a complete record and the last one the most complete.
+A plain run times the headline alone and prints one record.  With ``--full``, rank 0
+prints the complete record right after the headline and re-prints it, augmented, after
+every section; every line is a complete record and the last one the most complete.
 
 Runs the script end to end on CPU (gloo) with the ``--tiny`` model variant, at
 one rank and under ``torch.distributed.run`` with two ranks.
@@ -13,6 +14,7 @@ import subprocess
 import sys
 from typing import Optional
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,11 +32,14 @@ def _run(nproc: int, *extra: str) -> dict:
     return _run_lines(nproc, *extra)[-1]
 
 
-def _run_lines(nproc: int, *extra: str, env_extra: Optional[dict] = None) -> list:
+def _run_lines(nproc: int, *extra: str, env_extra: Optional[dict] = None,
+               full: bool = True, steps: int = 1) -> list:
+    """The records of one run: with ``--full`` (sections, probe, tuned balances) unless
+    ``full=False``, the plain run that times the headline alone."""
     env = dict(os.environ, CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES='', OMP_NUM_THREADS='2',
                **(env_extra or {}))
-    args = ['bench.py', '--gpus', str(nproc), '--steps', '1', '--warmup', '1', '--tiny',
-            '--batch', '4', '--chunks', '2', *extra]
+    args = ['bench.py', '--gpus', str(nproc), '--steps', str(steps), '--warmup', '1', '--tiny',
+            '--batch', '4', '--chunks', '2', *(['--full'] if full else []), *extra]
     if nproc > 1:
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
                f'--nproc-per-node={nproc}', '--master-addr', '127.0.0.1',
@@ -159,6 +164,66 @@ def test_bench_headline_uses_reference_balance_and_reports_tuned():
     tuned = rec['tuned']
     assert tuned is not None and tuned['value'] > 0 and sum(tuned['balance']) == sum(
         rec['config']['balance'])
+
+
+@pytest.mark.parametrize('nproc', [1, 2])
+def test_bench_plain_run_times_the_headline_alone(nproc):
+    """Without ``--full``: one record, the headline's, with ``--steps`` timed steps; no
+    section, no tuned balance, no receive-wait probe."""
+    records = _run_lines(nproc, '--model', 'unet', full=False, steps=2)
+    assert len(records) == 1
+    rec = records[0]
+    assert rec['n_gpus'] == nproc and rec['steps'] == 2 and rec['warmup'] == 1
+    assert rec['unit'] == 'samples/sec' and rec['higher_is_better'] is True
+    assert rec['dtype'] == 'fp32' and rec['ms_per_step'] > 0
+    assert rec['value'] == pytest.approx(4 * 1000 / rec['ms_per_step'], rel=1e-2)
+    assert set(rec['section_s']) == {'headline'} and rec['tuned'] is None
+    assert not {'baseline', 'gpipe', 'amoebanet', 'resnet101', 'per_rank', 'striped',
+                'amoebanet_graph_cells'} & set(rec)
+
+
+def test_bench_extras_need_full():
+    """Asking for a section, the tuned balance, the probe or profiler steps without
+    ``--full`` is a usage error, not a silently shorter run."""
+    for extra in (['--sections', 'baseline'], ['--also-tuned', 'yes'], ['--probe', 'on'],
+                  ['--profile-steps', '1'], ['--section-steps', '2']):
+        out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--tiny', *extra],
+                             cwd=ROOT, capture_output=True, text=True, timeout=300,
+                             env=dict(os.environ, CUDA_VISIBLE_DEVICES='',
+                                      HIP_VISIBLE_DEVICES=''))
+        assert out.returncode == 2 and '--full' in out.stderr, out.stderr[-1000:]
+        assert not out.stdout.strip()
+
+
+def test_bench_dump_outputs(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss, gradients and updated parameters
+    as float32 ``.npy`` files; weights and inputs are seeded, so two runs write the same."""
+    dumps = []
+    for name in ('a', 'b'):
+        d = tmp_path / name
+        records = _run_lines(1, '--model', 'unet', '--dump-outputs', str(d), full=False,
+                             steps=2)
+        assert len(records) == 1 and records[0]['steps'] == 2
+        assert sorted(p.name for p in d.iterdir()) == ['grads.npy', 'loss.npy', 'params.npy']
+        dumps.append({p.stem: np.load(p) for p in d.iterdir()})
+    first, second = dumps
+    assert first['loss'].shape == () and np.isfinite(first['loss'])
+    assert first['grads'].shape == first['params'].shape and first['grads'].ndim == 1
+    assert first['grads'].size > 0 and np.abs(first['grads']).max() > 0
+    for name, a in first.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        np.testing.assert_allclose(second[name], a, rtol=1e-5, atol=1e-7)
+
+
+def test_bench_dump_outputs_two_ranks(tmp_path):
+    """At N > 1 every rank writes its own partition's arrays; the loss comes from the last."""
+    _run_lines(2, '--model', 'unet', '--dump-outputs', str(tmp_path), full=False)
+    assert sorted(p.name for p in tmp_path.iterdir()) == [
+        'grads_rank0.npy', 'grads_rank1.npy', 'loss_rank1.npy', 'params_rank0.npy',
+        'params_rank1.npy']
+    for p in tmp_path.iterdir():
+        a = np.load(p)
+        assert a.dtype == np.float32 and np.isfinite(a).all()
 
 
 def test_bench_reference_balance_tables():
