@@ -388,6 +388,74 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(
   }
 }
 
+// Eval-mode BatchNorm (+ add) (+ ReLU): one workgroup per (channel, image range) folds the
+// channel's running statistics and affine into (mu, k, b) itself -- no fold launch -- and
+// runs the training normalise pass's loops (two quads / four elements per thread per round,
+// loads first).  x and y may be the same buffer: each value is read and written by one thread.
+template <bool kVec, bool kAdd, bool kRelu>
+__global__ __launch_bounds__(256) void bn_eval_act_kernel(
+    const float* x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ rm, const float* __restrict__ rv, float eps,
+    const float* __restrict__ add, float* y, int n, int c, int s, int n_per) {
+  const int ch = blockIdx.x, tid = threadIdx.x;
+  const float mu = rm[ch], k = rsqrtf(rv[ch] + eps) * (gamma ? gamma[ch] : 1.f);
+  const float bb = beta ? beta[ch] : 0.f;
+  const int n0 = blockIdx.y * n_per, n1 = min(n, n0 + n_per);
+  if constexpr (kVec) {
+    const int sq = s >> 2, quads = (n1 - n0) * sq;
+    for (int q0 = tid; q0 < quads; q0 += 2 * 256) {
+      int64_t o[2];
+      floatx4 xv[2], av[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int q = q0 + u * 256;
+        const int img = n0 + q / sq, p = q - (img - n0) * sq;
+        o[u] = (static_cast<int64_t>(img) * c + ch) * sq + p;
+        if (q < quads) {
+          xv[u] = reinterpret_cast<const floatx4*>(x)[o[u]];
+          if constexpr (kAdd) av[u] = reinterpret_cast<const floatx4*>(add)[o[u]];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (q0 + u * 256 >= quads) break;
+        // (x - mean) * k, not x * k - mean * k: no cancellation when |mean| >> std
+        floatx4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(xv[u][e] - mu, k, bb);
+        if constexpr (kAdd) v += av[u];
+        if constexpr (kRelu) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
+        reinterpret_cast<floatx4*>(y)[o[u]] = v;
+      }
+    }
+  } else {
+    const int elems = (n1 - n0) * s;
+    for (int e0 = tid; e0 < elems; e0 += 4 * 256) {
+      int64_t o[4];
+      float xv[4], av[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = e0 + u * 256;
+        const int img = n0 + e / s, p = e - (img - n0) * s;
+        o[u] = (static_cast<int64_t>(img) * c + ch) * s + p;
+        xv[u] = e < elems ? x[o[u]] : 0.f;
+        if constexpr (kAdd) av[u] = e < elems ? add[o[u]] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (e0 + u * 256 >= elems) break;
+        float v = __builtin_fmaf(xv[u] - mu, k, bb);
+        if constexpr (kAdd) v += av[u];
+        if constexpr (kRelu) v = v > 0.f ? v : 0.f;
+        y[o[u]] = v;
+      }
+    }
+  }
+}
+
 // One workgroup per (channel, image range): sums of dy and dy * (z - mean).
 // dy may be a channel slice of a wider tensor (the gradient of a concatenated cell
 // output): image `img` of dy starts at dy + img * dy_img (z and dz are dense).
@@ -869,6 +937,35 @@ void launch_bn_apply(const float* z, const float* mean, const float* invstd, con
       hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(grid), dim3(256), 0, stream, z,
                          mean, invstd, gamma, beta, add, y, total, c, s);
   }
+}
+
+void launch_bn_eval_act(const float* x, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, float eps,
+                        const float* add, float* y, int64_t n, int64_t c, int64_t s, bool relu,
+                        hipStream_t stream) {
+  if (n == 0 || c == 0 || s == 0) return;
+  // (channel, image range) workgroups, as launch_bn_finalize_apply: the chip covered ~4x
+  int64_t splits = (1024 + c - 1) / c;
+  if (splits > n) splits = n;
+  const int64_t n_per = (n + splits - 1) / splits;
+  splits = (n + n_per - 1) / n_per;
+  const dim3 grid(static_cast<unsigned>(c), static_cast<unsigned>(splits));
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, x, gamma, beta, running_mean,
+                       running_var, eps, add, y, static_cast<int>(n), static_cast<int>(c),
+                       static_cast<int>(s), static_cast<int>(n_per));
+  };
+  const bool vec = (s & 3) == 0;
+  if (relu && add) {
+    if (vec) go(bn_eval_act_kernel<true, true, true>);
+    else go(bn_eval_act_kernel<false, true, true>);
+  } else if (relu) {
+    if (vec) go(bn_eval_act_kernel<true, false, true>);
+    else go(bn_eval_act_kernel<false, false, true>);
+  } else if (vec && add) go(bn_eval_act_kernel<true, true, false>);
+  else if (vec) go(bn_eval_act_kernel<true, false, false>);
+  else if (add) go(bn_eval_act_kernel<false, true, false>);
+  else go(bn_eval_act_kernel<false, false, false>);
 }
 
 bool bn_backward_parts_ok(int64_t n, int64_t c, int64_t s) {

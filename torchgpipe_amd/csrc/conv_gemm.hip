@@ -516,7 +516,7 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
     const float* __restrict__ a_src, const float* __restrict__ b_src,
     const float* __restrict__ x_mask, float* __restrict__ out, float* __restrict__ part_mean,
     float* __restrict__ part_m2, Geo g, int M, int N, int K, int k_chunk, int64_t split_stride,
-    int accumulate, int64_t a_bytes, int64_t b_bytes, PhaseSet ps) {
+    int accumulate, int64_t a_bytes, int64_t b_bytes, PhaseSet ps, ConvGemmTail et) {
   using C = Cfg<CFG>;
   if constexpr (MODE == kBwdData) {
     // this workgroup's stride phase (grid.z: one phase's grid after the other -- phases
@@ -1023,59 +1023,95 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
   const int ch_off = MODE == kFwd ? g.co_off : 0;
   const __amdgpu_buffer_rsrc_t mr = rsrc(x_mask, x_mask ? static_cast<int64_t>(g.n) * g.ci *
                                                               hw_in * 4 : 0);
-  for (int idx = tid; idx < C::BM * kQuads; idx += kThreads) {
-    const int row = idx / kQuads, q = idx - row * kQuads;
-    const int m = m0 + row, j = n0 + 4 * q;
-    if (m >= M || j >= N) continue;
-    floatx4 v = *reinterpret_cast<const floatx4*>(ct + row * C::kCStride + 4 * q);
-    if (scatter) {
-      // strided 1x1 backward-data: output pixel (y, x) -> input (y*sh+oh, x*sw+ow)
+  // The store loop, compiled twice: as ever, and (forward launches given et.mean) with the
+  // inference tail -- this row's eval-mode BatchNorm folded from its four per-channel values
+  // (loads that hit cache, one rsqrt per row-quad), the node sum / residual and the output
+  // ReLU applied before the store.  One wave-uniform branch picks the loop, so the training
+  // launches run the instructions they always ran.
+  auto store_tile = [&](auto tail_c) {
+    constexpr bool kTail = decltype(tail_c)::value;
+    for (int idx = tid; idx < C::BM * kQuads; idx += kThreads) {
+      const int row = idx / kQuads, q = idx - row * kQuads;
+      const int m = m0 + row, j = n0 + 4 * q;
+      if (m >= M || j >= N) continue;
+      floatx4 v = *reinterpret_cast<const floatx4*>(ct + row * C::kCStride + 4 * q);
+      if (scatter) {
+        // strided 1x1 backward-data: output pixel (y, x) -> input (y*sh+oh, x*sw+ow)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int je = j + e;
-        if (je >= N) break;
-        const int n = g.fd_hwo.div(je), p = je - n * hw_out;
-        const int y = g.fd_wo.div(p), x = p - y * g.wo;
-        const int yi = y * g.sh - g.ph + g.oh, xi = x * g.sw - g.pw + g.ow;
-        if (yi < 0 || yi >= g.h || xi < 0 || xi >= g.w) continue;
-        const int64_t off = ((static_cast<int64_t>(n) * g.ci + m) * g.h + yi) * g.w + xi;
-        float val = v[e];
-        if (g.relu && !(bload(mr, static_cast<uint32_t>(off * 4)) > 0.f)) val = 0.f;
-        if (g.fill) {  // (host-checked: stride 2, even width, no padding, offset or accumulate)
-          *reinterpret_cast<floatx2*>(out + off) = floatx2{val, 0.f};
-          if (yi + 1 < g.h) *reinterpret_cast<floatx2*>(out + off + g.w) = floatx2{0.f, 0.f};
-          continue;
-        }
-        out[off] = accumulate ? out[off] + val : val;
-      }
-      continue;
-    }
-    const int n = fdh.div(j), p = j - n * hw;
-    const int64_t base = (static_cast<int64_t>(n) * ch_total + ch_off + m) * hw + p;
-    if ((hw & 3) == 0 && j + 3 < N) {
-      if constexpr (MODE == kBwdData) {
-        if (g.relu) {
-          const floatx4 xv = bload4(mr, static_cast<uint32_t>(base * 4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = xv[e] > 0.f ? v[e] : 0.f;
-        }
-      }
-      if (MODE == kBwdData && accumulate) v += *reinterpret_cast<const floatx4*>(out + base);
-      *reinterpret_cast<floatx4*>(out + base) = v;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int je = j + e;
-        if (je >= N) break;
-        const int ne = fdh.div(je), pe = je - ne * hw;
-        const int64_t off = (static_cast<int64_t>(ne) * ch_total + ch_off + m) * hw + pe;
-        float val = v[e];
-        if constexpr (MODE == kBwdData) {
+        for (int e = 0; e < 4; ++e) {
+          const int je = j + e;
+          if (je >= N) break;
+          const int n = g.fd_hwo.div(je), p = je - n * hw_out;
+          const int y = g.fd_wo.div(p), x = p - y * g.wo;
+          const int yi = y * g.sh - g.ph + g.oh, xi = x * g.sw - g.pw + g.ow;
+          if (yi < 0 || yi >= g.h || xi < 0 || xi >= g.w) continue;
+          const int64_t off = ((static_cast<int64_t>(n) * g.ci + m) * g.h + yi) * g.w + xi;
+          float val = v[e];
           if (g.relu && !(bload(mr, static_cast<uint32_t>(off * 4)) > 0.f)) val = 0.f;
+          if (g.fill) {  // (host-checked: stride 2, even width, no padding, offset or accumulate)
+            *reinterpret_cast<floatx2*>(out + off) = floatx2{val, 0.f};
+            if (yi + 1 < g.h) *reinterpret_cast<floatx2*>(out + off + g.w) = floatx2{0.f, 0.f};
+            continue;
+          }
+          out[off] = accumulate ? out[off] + val : val;
         }
-        out[off] = (MODE == kBwdData && accumulate) ? out[off] + val : val;
+        continue;
+      }
+      const int n = fdh.div(j), p = j - n * hw;
+      const int64_t base = (static_cast<int64_t>(n) * ch_total + ch_off + m) * hw + p;
+      float tk = 1.f, tmu = 0.f, tb = 0.f;
+      if constexpr (kTail) {
+        const int c = ch_off + m;
+        tk = rsqrtf(et.var[c] + et.eps) * (et.gamma ? et.gamma[c] : 1.f);
+        tmu = et.mean[c];
+        tb = et.beta ? et.beta[c] : 0.f;
+      }
+      if ((hw & 3) == 0 && j + 3 < N) {
+        if constexpr (kTail) {
+          // (z - mean) * k + beta: the training normalise pass's form, no cancellation
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(v[e] - tmu, tk, tb);
+          if (et.add) v += *reinterpret_cast<const floatx4*>(et.add + base);
+          if (et.relu_out) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+          }
+        }
+        if constexpr (MODE == kBwdData) {
+          if (g.relu) {
+            const floatx4 xv = bload4(mr, static_cast<uint32_t>(base * 4));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = xv[e] > 0.f ? v[e] : 0.f;
+          }
+        }
+        if (MODE == kBwdData && accumulate) v += *reinterpret_cast<const floatx4*>(out + base);
+        *reinterpret_cast<floatx4*>(out + base) = v;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int je = j + e;
+          if (je >= N) break;
+          const int ne = fdh.div(je), pe = je - ne * hw;
+          const int64_t off = (static_cast<int64_t>(ne) * ch_total + ch_off + m) * hw + pe;
+          float val = v[e];
+          if constexpr (MODE == kBwdData) {
+            if (g.relu && !(bload(mr, static_cast<uint32_t>(off * 4)) > 0.f)) val = 0.f;
+          }
+          if constexpr (kTail) {
+            val = __builtin_fmaf(val - tmu, tk, tb);
+            if (et.add) val += et.add[off];
+            if (et.relu_out) val = val > 0.f ? val : 0.f;
+          }
+          out[off] = (MODE == kBwdData && accumulate) ? out[off] + val : val;
+        }
       }
     }
+  };
+  if constexpr (MODE == kFwd) {
+    if (et.mean != nullptr) store_tile(std::true_type{});
+    else store_tile(std::false_type{});
+  } else {
+    store_tile(std::false_type{});
   }
 
   if constexpr (MODE == kFwd) {
@@ -1111,7 +1147,8 @@ template <int MODE, int CFG>
 void launch_cfg(const float* a, const float* b, const float* xm, float* out, float* pmean,
                 float* pm2, const Geo& g, int M, int N, int K, int splits, int64_t split_stride,
                 bool accumulate, int64_t a_bytes, int64_t b_bytes, hipStream_t stream,
-                const PhaseSet& ps = PhaseSet{}, bool pre_a = false) {
+                const PhaseSet& ps = PhaseSet{}, bool pre_a = false,
+                const ConvGemmTail& tail = ConvGemmTail{}) {
   using C = Cfg<CFG>;
   const int mb = (M + C::BM - 1) / C::BM, nb = (N + C::BN - 1) / C::BN;
   int k_chunk = (K + splits - 1) / splits;
@@ -1124,7 +1161,7 @@ void launch_cfg(const float* a, const float* b, const float* xm, float* out, flo
     hipLaunchKernelGGL((conv_gemm_kernel<MODE, CFG, decltype(plain_c)::value,
                                          decltype(pre_c)::value>),
                        grid, block, 0, stream, a, b, xm, out, pmean, pm2, g, M, N, K, k_chunk,
-                       split_stride, accumulate ? 1 : 0, a_bytes, b_bytes, ps);
+                       split_stride, accumulate ? 1 : 0, a_bytes, b_bytes, ps, tail);
   };
   using T = std::true_type;
   using F = std::false_type;
@@ -1178,11 +1215,14 @@ __global__ __launch_bounds__(256) void conv_gemm_presplit_kernel(const float* __
 // accumulators (16 loads in flight per lane), then the waves combine through LDS: the
 // weight gradient's 30-60-way splits no longer walk a serial chain of dependent loads
 // per element (measured 12 us for 62 x 64 KiB partials with one lane per element).
-template <bool kVec>
+// kTail (forward partials of an eval-mode Conv-BN): the folded BatchNorm, node sum and
+// output ReLU of ConvGemmTail applied to the sum before the store (kVec then means
+// hw % 4 == 0: a quad stays inside one channel plane).
+template <bool kVec, bool kTail = false>
 __global__ __launch_bounds__(256) void split_reduce_kernel(
     const float* __restrict__ ws, int splits, int64_t stride, float* __restrict__ out,
     const float* __restrict__ mask, int accumulate, int64_t total, int64_t c, int64_t hw,
-    int64_t c_total, int64_t c_off) {
+    int64_t c_total, int64_t c_off, ConvGemmTail et) {
   constexpr int kE = kVec ? 4 : 1;
   typedef float V __attribute__((ext_vector_type(kE)));
   __shared__ V part[3][64];
@@ -1215,28 +1255,47 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(
 #pragma unroll
     for (int e = 0; e < kE; ++e) v[e] = m[e] > 0.f ? v[e] : 0.f;
   }
+  if constexpr (kTail) {
+    const int64_t ch = c_off + r / hw;
+    const float k = rsqrtf(et.var[ch] + et.eps) * (et.gamma ? et.gamma[ch] : 1.f);
+    const float mu = et.mean[ch], b = et.beta ? et.beta[ch] : 0.f;
+#pragma unroll
+    for (int e = 0; e < kE; ++e) v[e] = __builtin_fmaf(v[e] - mu, k, b);
+    if (et.add) v += *reinterpret_cast<const V*>(et.add + o);
+    if (et.relu_out) {
+#pragma unroll
+      for (int e = 0; e < kE; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+    }
+  }
   if (accumulate) v += *dst;
   *dst = v;
 }
 
 void launch_split_reduce(const float* ws, int splits, int64_t stride, float* out,
                          const float* mask, bool accumulate, int64_t planes, int64_t c,
-                         int64_t hw, int64_t c_total, int64_t c_off, hipStream_t stream) {
+                         int64_t hw, int64_t c_total, int64_t c_off, hipStream_t stream,
+                         const ConvGemmTail& tail = ConvGemmTail{}) {
   const int64_t total = planes * c * hw;
   if (total == 0) return;
+  const bool has_tail = tail.mean != nullptr;
   // quads never straddle a channel plane when hw % 4 == 0, and a single dense output
   // (backward-data / weight-gradient partials: planes 1, hw 1) is one flat array
-  const bool flat = planes == 1 && c_off == 0 && c_total == c;
+  const bool flat = planes == 1 && c_off == 0 && c_total == c && !has_tail;
   const bool vec = ((hw & 3) == 0 || (flat && (total & 3) == 0)) && (stride & 3) == 0;
   const int64_t items = vec ? total / 4 : total;
   const unsigned blocks = static_cast<unsigned>((items + 63) / 64);
-  if (vec)
-    hipLaunchKernelGGL(split_reduce_kernel<true>, dim3(blocks), dim3(256), 0, stream, ws, splits,
-                       stride, out, mask, accumulate ? 1 : 0, total, c, hw, c_total, c_off);
-  else
-    hipLaunchKernelGGL(split_reduce_kernel<false>, dim3(blocks), dim3(256), 0, stream, ws,
-                       splits, stride, out, mask, accumulate ? 1 : 0, total, c, hw, c_total,
-                       c_off);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, ws, splits, stride, out, mask,
+                       accumulate ? 1 : 0, total, c, hw, c_total, c_off, tail);
+  };
+  if (has_tail) {
+    if (vec) go(split_reduce_kernel<true, true>);
+    else go(split_reduce_kernel<false, true>);
+  } else if (vec) {
+    go(split_reduce_kernel<true>);
+  } else {
+    go(split_reduce_kernel<false>);
+  }
 }
 
 // Forward split reduction fused with the BatchNorm statistics pass: one wave per (image,
@@ -1693,13 +1752,19 @@ void launch_conv_gemm(int mode, const float* a, const float* b, const float* x_m
   float* pm = split ? nullptr : part_mean;
   float* pm2 = split ? nullptr : part_m2;
   const bool acc = accumulate && !split;
+  // the inference tail goes with the launch that stores the output: the GEMM's epilogue,
+  // or the reduction of a split plan's partials
+  const bool has_tail = cg.tail.mean != nullptr;
+  if (has_tail && (mode != kFwd || part_mean != nullptr || accumulate))
+    throw std::runtime_error("conv_gemm: the inference tail is for a plain forward launch");
+  const ConvGemmTail gemm_tail = split ? ConvGemmTail{} : cg.tail;
   if (cg.a_split && (mode == kWgrad || !conv_gemm_emu_cfg(plan.cfg) || cg.phase))
     throw std::runtime_error("conv_gemm: a pre-split A needs a split-bf16 forward / "
                              "backward-data plan");
   auto go = [&](auto mode_c, auto cfg_c, float* p1, float* p2, const float* mask) {
     launch_cfg<decltype(mode_c)::value, decltype(cfg_c)::value>(
         a, b, mask, dst, p1, p2, gk, M, N, K, plan.splits, stride, acc, a_bytes, b_bytes,
-        stream, PhaseSet{}, cg.a_split);
+        stream, PhaseSet{}, cg.a_split, gemm_tail);
   };
   using F = std::integral_constant<int, kFwd>;
   using D = std::integral_constant<int, kBwdData>;
@@ -1731,7 +1796,7 @@ void launch_conv_gemm(int mode, const float* a, const float* b, const float* x_m
     planes = 1; c = static_cast<int64_t>(M) * N; hw = 1; c_total = c;
   }
   launch_split_reduce(ws, plan.splits, stride, out, mode == kBwdData && g.relu ? x_mask : nullptr,
-                      accumulate, planes, c, hw, c_total, c_off, stream);
+                      accumulate, planes, c, hw, c_total, c_off, stream, cg.tail);
 }
 
 void launch_conv_gemm_partials(const float* a, const float* b, float* ws, const ConvGemmGeo& cg,

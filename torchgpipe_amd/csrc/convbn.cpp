@@ -742,6 +742,96 @@ std::vector<at::Tensor> convbn_forward(const at::Tensor& x_in, at::TensorList we
   return {y, z, mean, invstd, sums};
 }
 
+// `add` as the kernels read it: dense, the output's shape, 16-byte aligned (float4 loads).
+at::Tensor dense_add(const at::Tensor& add, const at::Tensor& like) {
+  TORCH_CHECK(add.sizes() == like.sizes(), "add must have the output's shape");
+  auto a = add.contiguous();
+  if ((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) != 0) a = a.clone();
+  check_f32(a, "add", like);
+  return a;
+}
+
+// Forward (evaluation): y = relu_out?(bn_eval(cat_i conv_i(relu?(x))) (+ add)) with the
+// BatchNorm folded from its running statistics inside the launch that stores y -- the GEMM's
+// epilogue, or the reduction of a split plan's partials (ConvGemmTail).  Forward plans, the
+// plan table and the pre-split weights are the training forward's.  Only y (and a split
+// plan's workspace) is allocated, nothing synchronises, the running buffers are only read:
+// the op can be captured in a hipGraph.
+at::Tensor convbn_eval_forward(const at::Tensor& x_in, at::TensorList weights,
+                               at::IntArrayRef geo, bool relu,
+                               const c10::optional<at::Tensor>& gamma,
+                               const c10::optional<at::Tensor>& beta,
+                               const at::Tensor& running_mean, const at::Tensor& running_var,
+                               double eps, const c10::optional<at::Tensor>& add, bool relu_out) {
+  auto x = x_in.contiguous();
+  check_f32(x, "x", x);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Parts p = make_parts(x, weights, geo, relu);
+  const int64_t c = p.co_total;
+  auto y = at::empty({x.size(0), c, p.ho, p.wo}, x.options());
+  ConvGemmTail tail;
+  tail.gamma = opt_ptr(gamma, "gamma", x, c);
+  tail.beta = opt_ptr(beta, "beta", x, c);
+  tail.mean = opt_ptr(running_mean, "running_mean", x, c);
+  tail.var = opt_ptr(running_var, "running_var", x, c);
+  TORCH_CHECK(tail.mean != nullptr && tail.var != nullptr, "running statistics are required");
+  tail.eps = static_cast<float>(eps);
+  tail.relu_out = relu_out ? 1 : 0;
+  at::Tensor add_c;
+  if (add.has_value() && add->defined()) {
+    add_c = dense_add(*add, y);
+    tail.add = add_c.data_ptr<float>();
+  }
+  if (y.numel() == 0) return y;
+  for (size_t i = 0; i < p.geo.size(); ++i) {
+    const auto& wt = weights[i];
+    // (a plan is found without the tail: tuning candidates write the raw convolution)
+    const ConvGemmPlan plan =
+        tuned_plan(0, wt.data_ptr<float>(), x.data_ptr<float>(), nullptr, y.data_ptr<float>(),
+                   nullptr, nullptr, p.geo[i], false, wt.numel() * 4, x.numel() * 4, x,
+                   y.numel(), ASource{&weights[i], false});
+    ConvGemmGeo g = p.geo[i];
+    g.tail = tail;
+    run_gemm(0, wt.data_ptr<float>(), x.data_ptr<float>(), nullptr, y.data_ptr<float>(), nullptr,
+             nullptr, g, plan, false, wt.numel() * 4, x.numel() * 4, x,
+             ASource{&weights[i], false});
+  }
+  return y;
+}
+
+// Eval-mode BatchNorm2d (+ add) (+ ReLU) of a tensor some other convolution produced
+// (Winograd, MIOpen) or of an unlinked BatchNorm: one pass, the fold inside the kernel;
+// `inplace` writes over x (a fresh convolution output) and returns it.
+at::Tensor bn_eval_act(const at::Tensor& x_in, const c10::optional<at::Tensor>& gamma,
+                       const c10::optional<at::Tensor>& beta, const at::Tensor& running_mean,
+                       const at::Tensor& running_var, double eps,
+                       const c10::optional<at::Tensor>& add, bool relu, bool inplace) {
+  TORCH_CHECK(x_in.dim() >= 2, "x must be [N][C][*]");
+  TORCH_CHECK(!inplace || x_in.is_contiguous(), "in place needs a contiguous x");
+  auto x = x_in.contiguous();
+  check_f32(x, "x", x);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  if ((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) != 0) {  // (float4 loads)
+    TORCH_CHECK(!inplace, "in place needs a 16-byte aligned x");
+    x = x.clone();
+  }
+  const int64_t n = x.size(0), c = x.size(1), s = n * c == 0 ? 0 : x.numel() / (n * c);
+  auto y = inplace ? x : at::empty_like(x);
+  const float* rm = opt_ptr(running_mean, "running_mean", x, c);
+  const float* rv = opt_ptr(running_var, "running_var", x, c);
+  TORCH_CHECK(rm != nullptr && rv != nullptr, "running statistics are required");
+  const float* ad = nullptr;
+  at::Tensor add_c;
+  if (add.has_value() && add->defined()) {
+    add_c = dense_add(*add, x);
+    ad = add_c.data_ptr<float>();
+  }
+  launch_bn_eval_act(x.data_ptr<float>(), opt_ptr(gamma, "gamma", x, c),
+                     opt_ptr(beta, "beta", x, c), rm, rv, static_cast<float>(eps), ad,
+                     y.data_ptr<float>(), n, c, s, relu, cur_stream(x));
+  return y;
+}
+
 // Backward: returns {dx (undefined unless need_dx), dgamma, dbeta, dw_0, dw_1, ...}.
 // `sums` is the forward's zeroed [2][C] buffer (consumed).  `accum` is empty or holds one
 // optional entry per parameter gradient {dgamma, dbeta, dw_0, ...}: a given tensor (the
@@ -1739,6 +1829,11 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
         "Tensor? beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
         "Tensor(c!)? num_batches_tracked, float momentum, float eps, Tensor? add, "
         "bool relu_out=False) -> Tensor[]");
+  m.def("convbn_eval_forward(Tensor x, Tensor[] weights, int[] geo, bool relu, Tensor? gamma, "
+        "Tensor? beta, Tensor running_mean, Tensor running_var, float eps, Tensor? add, "
+        "bool relu_out=False) -> Tensor");
+  m.def("bn_eval_act(Tensor x, Tensor? gamma, Tensor? beta, Tensor running_mean, "
+        "Tensor running_var, float eps, Tensor? add, bool relu, bool inplace=False) -> Tensor");
   m.def("convbn_backward(Tensor dy, Tensor x, Tensor z, Tensor mean, Tensor invstd, "
         "Tensor(a!) sums, Tensor? gamma, Tensor[] weights, int[] geo, bool relu, bool need_dx, "
         "Tensor?[] accum, Tensor[] weights_t, bool defer_wgrad, Tensor?[] slabs, "
@@ -1775,6 +1870,8 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
 
 TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("convbn_forward", &tgpipe::convbn_forward);
+  m.impl("convbn_eval_forward", &tgpipe::convbn_eval_forward);
+  m.impl("bn_eval_act", &tgpipe::bn_eval_act);
   m.impl("convbn_backward", &tgpipe::convbn_backward);
   m.impl("convbn_wgrad", &tgpipe::convbn_wgrad);
   m.impl("convbn_group_forward", &tgpipe::convbn_group_forward);

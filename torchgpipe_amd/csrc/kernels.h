@@ -157,6 +157,19 @@ void launch_wino_wgrad(const float* x, const float* dy, float* dw, float* ws, in
 
 // Implicit-GEMM convolution, NCHW fp32: 1x1 with any stride / offset, any kh x kw at
 // stride 1 (AmoebaNet's 1x1 / 1x7 / 7x1, U-Net's 3-channel input and 1x1 output convs).
+// Inference tail of a forward launch: an eval-mode BatchNorm folded into the store loop (or
+// into the split reduction), y = (z - mean[c]) * rsqrt(var[c] + eps) * gamma[c] + beta[c]
+// (+ add, the output's layout) (then max(., 0) when relu_out), c = co_off + row over co_total
+// channels.  gamma / beta null: 1 / 0.  mean null: no tail, the launch stores z as ever.
+struct ConvGemmTail {
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  const float* mean = nullptr;
+  const float* var = nullptr;
+  const float* add = nullptr;
+  float eps = 0.f;
+  int relu_out = 0;
+};
 struct ConvGemmGeo {
   int n, ci, h, w;       // input
   int co, ho, wo;        // output of this convolution
@@ -177,6 +190,9 @@ struct ConvGemmGeo {
   // operand pre-split into bf16 planes ([M][ceil(K/8)][hi, mid, lo][8], conv_gemm_presplit),
   // a_bytes its size -- the kernel stages it without splitting
   bool a_split = false;
+  // forward only, without statistics partials: the folded eval-mode BatchNorm (+ add)
+  // (+ ReLU) applied by the launch that stores the output
+  ConvGemmTail tail;
 };
 // Sub-pixel decomposition of a strided convolution's backward-data: input pixels of one
 // residue (a, b) modulo the stride receive exactly the taps th = th0 + sh*i, tw = tw0 + sw*j,
@@ -279,6 +295,13 @@ void launch_dbn_commit64(double* acc, float* running_mean, float* running_var, i
 void launch_bn_apply(const float* z, const float* mean, const float* invstd, const float* gamma,
                      const float* beta, const float* add, float* y, int64_t n, int64_t c,
                      int64_t s, hipStream_t stream);
+// Eval-mode BatchNorm (+ add) (+ ReLU) from the running statistics, folded in the kernel:
+// y = relu?((x - running_mean) * rsqrt(running_var + eps) * gamma + beta (+ add)); gamma /
+// beta null: 1 / 0.  y may be x (in place).
+void launch_bn_eval_act(const float* x, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, float eps,
+                        const float* add, float* y, int64_t n, int64_t c, int64_t s, bool relu,
+                        hipStream_t stream);
 // Backward: sums[2][C] (zeroed, e.g. by the forward's finalize) += (sum dy,
 // sum dy*(z-mean)); then
 // dz = gamma*invstd*(dy - sum_dy/M - (z-mean)*invstd^2*sum_dyz/M), dgamma, dbeta.

@@ -29,6 +29,7 @@ from typing import Callable, Dict, Iterator, List, Optional, Tuple, Union
 import torch
 from torch import Tensor, nn
 
+from torchgpipe_amd.ops import convbn
 from torchgpipe_amd.ops.convbn import (FusedChain, ReLUConvBN, _GroupCache, fusable,
                                        fused_triplets, group_relu_conv_bn, groupable,
                                        relu_conv_bn)
@@ -179,6 +180,8 @@ class FactorizedReduce(nn.Module):
             # both strided branches in one op: the second reads x shifted by one pixel
             # (the zero pad of the reference falls out of the bounds check)
             return relu_conv_bn(x, [(self.conv1, 0), (self.conv2, 1)], self.bn, add=add)
+        if convbn.eval_fusable(x, [self.conv1, self.conv2], self.bn, add):
+            return convbn.conv_bn_eval(x, [(self.conv1, 0), (self.conv2, 1)], self.bn, add=add)
         x = self.relu(x)
         shifted = self.pad(x[:, :, 1:, 1:])
         out = self.bn(torch.cat([self.conv1(x), self.conv2(shifted)], dim=1))
@@ -281,6 +284,8 @@ class Stem(nn.Module):
     def forward(self, x: Tensor) -> Tensor:  # type: ignore[override]
         if fusable(x, [self.conv], self.bn):
             return relu_conv_bn(x, [(self.conv, 0)], self.bn)
+        if convbn.eval_fusable(x, [self.conv], self.bn):
+            return convbn.conv_bn_eval(x, [(self.conv, 0)], self.bn)
         return self.bn(self.conv(self.relu(x)))
 
 

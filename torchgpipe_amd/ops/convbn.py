@@ -17,8 +17,21 @@ except for the stem and the stride-2 3×3 of the reduction cells they are 1×1,
 
 :class:`ReLUConvBN` / :class:`FusedChain` are ``nn.Sequential`` subclasses with
 the reference's children (``ReLU``, ``Conv2d``, ``BatchNorm2d`` …), so the
-state-dict keys are unchanged; they fall back to the eager modules on CPU, in
-eval mode, for non-fp32 tensors or unsupported convolutions.
+state-dict keys are unchanged; they fall back to the eager modules on CPU, for
+non-fp32 tensors or unsupported convolutions.
+
+Evaluation (``model.eval()``) has its own forward-only op, :func:`conv_bn_eval`: an
+eval-mode BatchNorm is a per-channel scale and shift, folded from the running
+statistics inside the implicit GEMM's store loop together with the node sum and the
+output ReLU -- one launch per triplet (a split-K plan: the GEMM and its reduction), no
+statistics, no saved ``z``, the running buffers untouched.  The remaining eager cases
+in eval: anything that needs a gradient while gradients are enabled (there is no
+backward through the eval op, so frozen-BatchNorm fine-tuning runs eagerly), a
+BatchNorm without running statistics (it normalises with batch statistics),
+``DeferredBatchNorm``, and the grouped three-way op (:func:`group_relu_conv_bn`; each of
+its triplets takes the single-op eval path instead).  The Winograd 3×3 path applies
+the BatchNorm as a separate in-place pass (``ops.fusion.bn_eval_act``) rather than in its
+output transform.
 """
 import contextlib
 import os
@@ -33,7 +46,7 @@ from torchgpipe_amd.ops.conv import _TransformCache
 
 __all__ = ['relu_conv_bn', 'ReLUConvBN', 'FusedChain', 'conv_supported', 'fused_triplets',
            'fusable', 'disabled', 'GemmConv2d', 'gemm_conv2d', 'gemm_conv_eligible',
-           'group_relu_conv_bn', 'groupable']
+           'group_relu_conv_bn', 'groupable', 'conv_bn_eval', 'eval_fusable']
 
 # TGPIPE_FUSED_CONVBN=0 runs the eager ReLU / Conv2d / BatchNorm2d modules instead.
 _ENABLED = os.environ.get('TGPIPE_FUSED_CONVBN', '1') != '0'
@@ -71,6 +84,25 @@ def _bn_ok(bn: nn.Module, x: Tensor) -> bool:
     return (isinstance(bn, nn.BatchNorm2d) and bn.training and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4
             and (bn.momentum is not None or not bn.track_running_stats))
+
+
+def _no_grad_needed(*tensors: Optional[Tensor]) -> bool:
+    return not torch.is_grad_enabled() or \
+        not any(t is not None and t.requires_grad for t in tensors)
+
+
+def _bn_eval_ok(bn: nn.Module, x: Tensor, add: Optional[Tensor] = None) -> bool:
+    """An eval-mode BatchNorm2d the native inference kernels take: fp32 NCHW on the GPU,
+    normalising with its running statistics, and nothing that needs a gradient (the eval
+    ops are forward-only)."""
+    return (_ENABLED and isinstance(bn, nn.BatchNorm2d) and not bn.training and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 4
+            and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None
+            and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device
+            and (bn.weight is None or bn.weight.dtype == torch.float32)
+            and (add is None or (add.dtype == torch.float32 and add.device == x.device))
+            and _no_grad_needed(x, add, bn.weight, bn.bias))
 
 
 # devices whose backward currently runs weight gradients on a side stream -> scope depth
@@ -245,6 +277,13 @@ def relu_conv_bn(x: Tensor, convs: Sequence[Tuple[nn.Conv2d, int]], bn: nn.Batch
     (one pair for ReLU-Conv-BN, two for FactorizedReduce: offsets 0 and 1).  Runs the
     fused HIP op when :func:`fusable`; callers check that first.
     """
+    weights = [conv.weight for conv, _ in convs]
+    return _ConvBN.apply(x, add, bn.weight, bn.bias, bn, _geo_of(convs), relu, relu_out,
+                         [_weight_cache(conv) for conv, _ in convs], (sink_in, sink_out),
+                         *weights)
+
+
+def _geo_of(convs: Sequence[Tuple[nn.Conv2d, int]]) -> List[int]:
     geo: List[int] = []
     for conv, offset in convs:
         # (the module's geometry, built once per offset: every micro-batch asks)
@@ -252,10 +291,21 @@ def relu_conv_bn(x: Tensor, convs: Sequence[Tuple[nn.Conv2d, int]], bn: nn.Batch
         if cached is None or cached[0] != offset:
             cached = conv.__dict__['_convbn_geo'] = (offset, _geo(conv, offset))
         geo += cached[1]
-    weights = [conv.weight for conv, _ in convs]
-    return _ConvBN.apply(x, add, bn.weight, bn.bias, bn, geo, relu, relu_out,
-                         [_weight_cache(conv) for conv, _ in convs], (sink_in, sink_out),
-                         *weights)
+    return geo
+
+
+def conv_bn_eval(x: Tensor, convs: Sequence[Tuple[nn.Conv2d, int]], bn: nn.BatchNorm2d,
+                 relu: bool = True, add: Optional[Tensor] = None,
+                 relu_out: bool = False) -> Tensor:
+    """:func:`relu_conv_bn` for evaluation: the same expression with ``bn`` normalising by its
+    running statistics, as one implicit-GEMM launch whose store loop applies the folded
+    BatchNorm, the sum and the output ReLU (a split-K plan: the GEMM and its reduction).
+    Forward only; the running buffers are read, never written.  Callers check
+    :func:`eval_fusable` first."""
+    with torch.no_grad():
+        return _ext.require(x).convbn_eval_forward(
+            x, [conv.weight for conv, _ in convs], _geo_of(convs), relu, bn.weight, bn.bias,
+            bn.running_mean, bn.running_var, float(bn.eps), add, relu_out)
 
 
 def _weight_cache(conv: nn.Module) -> _TransformCache:
@@ -273,6 +323,20 @@ _LIMIT = (1 << 31) - 64  # 32-bit buffer offsets of the kernels
 def fusable(x: Tensor, convs: Sequence[nn.Conv2d], bn: nn.Module) -> bool:
     if not (_ENABLED and _bn_ok(bn, x)):
         return False
+    return _convs_ok(x, convs)
+
+
+def eval_fusable(x: Tensor, convs: Sequence[nn.Conv2d], bn: nn.Module,
+                 add: Optional[Tensor] = None) -> bool:
+    """Whether :func:`conv_bn_eval` takes these convolutions and this BatchNorm: the
+    conditions of :func:`fusable` with an eval-mode BatchNorm that has running statistics,
+    and nothing -- ``x``, ``add``, the weights, gamma, beta -- needing a gradient."""
+    if not _bn_eval_ok(bn, x, add):
+        return False
+    return _convs_ok(x, convs) and _no_grad_needed(*[c.weight for c in convs])
+
+
+def _convs_ok(x: Tensor, convs: Sequence[nn.Conv2d]) -> bool:
     numel = x.numel()
     if numel * 4 >= _LIMIT:
         return False
@@ -310,9 +374,10 @@ class FusedChain(nn.Sequential):
     """A chain of (ReLU, Conv2d, BatchNorm2d) triplets run as fused ops.
 
     Children are the plain modules (the reference's state-dict keys); any triplet
-    the fused op does not cover (biased / grouped / dilated convolutions, eval-mode
-    BatchNorm, CPU tensors) runs eagerly.  ``add`` is folded into the last
-    triplet's normalisation pass.
+    the fused ops do not cover (biased / grouped / dilated convolutions, CPU tensors, an
+    eval-mode BatchNorm without running statistics or with gradients needed) runs eagerly;
+    an eval-mode BatchNorm otherwise takes :func:`conv_bn_eval`.  ``add`` is folded into the
+    last triplet's normalisation pass.
     """
 
     def forward(self, x: Tensor, add: Optional[Tensor] = None,  # type: ignore[override]
@@ -331,6 +396,8 @@ class FusedChain(nn.Sequential):
             extra = add if k == last else None
             if fusable(x, [conv], bn):
                 x = relu_conv_bn(x, [(conv, 0)], bn, relu=relu, add=extra)
+            elif eval_fusable(x, [conv], bn, extra):
+                x = conv_bn_eval(x, [(conv, 0)], bn, relu=relu, add=extra)
             else:
                 x = bn(conv(F.relu(x) if relu else x))
                 if extra is not None:

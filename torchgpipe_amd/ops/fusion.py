@@ -31,8 +31,16 @@ Links are only made between consecutive layers of one ``nn.Sequential`` -- one p
 partition -- so a balance that separates a convolution from its BatchNorm leaves both
 running on their own.  ``GPipe`` and ``PipelineStage`` call :func:`relink` on every
 partition after splitting (and after DeferredBatchNorm conversion, whose BatchNorms are
-not linked).  Outside training mode, on the CPU, or for non-fp32 tensors every layer runs
-its plain PyTorch forward.
+not linked).  On the CPU or for non-fp32 tensors every layer runs its plain PyTorch forward.
+
+Evaluation (``model.eval()`` with nothing needing a gradient) takes the same branches on
+forward-only ops: the pointwise and ``STRIDED_FUSED`` convolutions and the residual join
+run ``ops.convbn.conv_bn_eval`` (the BatchNorm folded from its running statistics into the
+GEMM's store loop, with the identity add and the ReLU: one launch), the Winograd and the
+other strided convolutions are followed by :func:`bn_eval_act` in place on their output,
+and an unlinked :class:`BatchNormAct2d` runs :func:`bn_eval_act` with its linked ReLU.  A
+BatchNorm without running statistics, ``DeferredBatchNorm``, and an eval forward that needs
+gradients stay on the plain PyTorch forward.
 """
 import os
 from typing import Callable, Dict, Optional
@@ -41,13 +49,13 @@ import torch
 from torch import Tensor, nn
 import torch.nn.functional as F
 
-from torchgpipe_amd.ops import _ext, gradacc
+from torchgpipe_amd.ops import _ext, convbn, gradacc
 from torchgpipe_amd.ops.conv import WinogradConv2d, conv_with_bn_stats, wino_eligible
-from torchgpipe_amd.ops.convbn import (GradSink, _bn_ok, fusable, gemm_conv2d,
+from torchgpipe_amd.ops.convbn import (GradSink, _bn_eval_ok, _bn_ok, fusable, gemm_conv2d,
                                        gemm_conv_eligible, relu_conv_bn)
 
 __all__ = ['ConvBN2d', 'BatchNormAct2d', 'ReLU', 'Linear', 'relink', 'bn_act', 'add_relu',
-           'pending_join']
+           'pending_join', 'bn_eval_act']
 
 _LINK = '_tgpipe_link'       # ConvBN2d -> (BatchNormAct2d, relu?)
 _RELU = '_tgpipe_relu_next'  # BatchNormAct2d -> a linked ReLU follows
@@ -115,6 +123,23 @@ def bn_act(x: Tensor, bn: nn.BatchNorm2d, relu: bool, part: Optional[Tensor] = N
     return _BNAct.apply(x.contiguous(), bn.weight, bn.bias, bn, relu, part, part_images)
 
 
+def _native_bn_eval_ok(bn: nn.Module, x: Tensor, add: Optional[Tensor] = None) -> bool:
+    return _bn_eval_ok(bn, x, add) and x.numel() > 0 and x.numel() * 4 < (1 << 31) - 64 \
+        and _ext.available()
+
+
+def bn_eval_act(x: Tensor, bn: nn.BatchNorm2d, relu: bool, add: Optional[Tensor] = None,
+                inplace: bool = False) -> Tensor:
+    """``relu(bn(x) + add)`` (ReLU and ``add`` optional) for an eval-mode ``bn``: one native
+    pass that folds the running statistics and the affine itself; ``inplace`` writes over
+    ``x`` (a fresh convolution output).  Forward only; callers check
+    :func:`_native_bn_eval_ok` first."""
+    with torch.no_grad():
+        return _ext.require(x).bn_eval_act(
+            x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), add, relu,
+            inplace and x.is_contiguous())
+
+
 def _mark(y: Tensor, bn: nn.Module, relu: bool) -> Tensor:
     setattr(y, _DONE_BN, id(bn))
     if relu:
@@ -159,7 +184,17 @@ def pending_join(x: Tensor, join: nn.Module, identity: Tensor) -> Optional[Tenso
         return None
     conv, bn, _ = pend
     n, _, h, w = x.shape
-    if identity.shape != (n, conv.out_channels, h, w) or identity.dtype != x.dtype:
+    if not bn.training:
+        # evaluation: convolution, folded BatchNorm, identity add and ReLU in one launch
+        same = identity.shape == (n, conv.out_channels, h, w)
+        if same and convbn.eval_fusable(x, [conv], bn, identity):
+            y = convbn.conv_bn_eval(x, [(conv, 0)], bn, relu=False, add=identity,
+                                    relu_out=True)
+        elif convbn.eval_fusable(x, [conv], bn):
+            y = F.relu(convbn.conv_bn_eval(x, [(conv, 0)], bn, relu=False) + identity)
+        else:
+            y = F.relu(nn.BatchNorm2d.forward(bn, nn.Conv2d.forward(conv, x)) + identity)
+    elif identity.shape != (n, conv.out_channels, h, w) or identity.dtype != x.dtype:
         y = relu_conv_bn(x, [(conv, 0)], bn, relu=False) + identity
         y = F.relu(y)
     else:
@@ -214,6 +249,11 @@ STRIDED_FUSED = frozenset({
 })
 
 
+def _in_strided_set(conv: nn.Conv2d, x: Tensor) -> bool:
+    return (conv.in_channels, conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride),
+            tuple(conv.padding), x.shape[2]) in STRIDED_FUSED  # type: ignore[arg-type]
+
+
 def _strided_fused(conv: nn.Conv2d, bn: nn.BatchNorm2d, x: Tensor, relu: bool) -> bool:
     """Whether one strided Conv-BN(-ReLU) runs as the fused native op: the shipped measured
     set (``STRIDED_FUSED``), or with ``TGPIPE_STRIDED_CHOICE=1`` both ways timed on the first
@@ -221,9 +261,8 @@ def _strided_fused(conv: nn.Conv2d, bn: nn.BatchNorm2d, x: Tensor, relu: bool) -
     gradients and running statistics are untouched; inside a stream capture an undecided
     geometry stays on MIOpen)."""
     if not STRIDED_CHOICE:
-        return (conv.in_channels, conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride),
-                tuple(conv.padding), x.shape[2]) in STRIDED_FUSED  # type: ignore[arg-type]
-    key = (tuple(x.shape), conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride),
+        return _in_strided_set(conv, x)
+    key =(tuple(x.shape), conv.out_channels, tuple(conv.kernel_size), tuple(conv.stride),
            tuple(conv.padding), relu, x.device)  # type: ignore[arg-type]
     hit = _STRIDED.get(key)
     if hit is not None:
@@ -274,6 +313,9 @@ class ConvBN2d(WinogradConv2d):
             input, self.weight, self.stride, self.padding, self.dilation, self.groups)
         if link is not None and self.padding_mode == 'zeros':
             bn, relu, join = link
+            if (self.bias is None and not bn.training and _native_bn_eval_ok(bn, input)
+                    and convbn._no_grad_needed(self.weight)):
+                return self._eval_forward(input, bn, relu, join, wino)
             if (join is not None and self.bias is None and _pointwise(self)
                     and _native_bn_ok(bn, input) and fusable(input, [self], bn)):
                 # the residual join right after the BatchNorm runs this convolution, the
@@ -312,6 +354,26 @@ class ConvBN2d(WinogradConv2d):
             return gemm_conv2d(input, self)
         return gradacc.library_conv2d(input, self)
 
+    def _eval_forward(self, input: Tensor, bn: nn.BatchNorm2d, relu: bool,
+                      join: Optional[nn.Module], wino: bool) -> Tensor:
+        """The linked BatchNorm in eval mode (the caller checked it): the training branches on
+        the forward-only ops."""
+        fused = convbn.eval_fusable(input, [self], bn)
+        if join is not None and _pointwise(self) and fused:
+            # left for the residual join, as in training (pending_join)
+            out = input.view_as(input)
+            setattr(out, _PENDING, (self, bn, join))
+            setattr(out, _DONE_BN, id(bn))
+            return out
+        if wino:
+            z = WinogradConv2d.forward(self, input)
+            return _mark(bn_eval_act(z, bn, relu, inplace=True), bn, relu)
+        if fused and (_pointwise(self) or _in_strided_set(self, input)):
+            y = convbn.conv_bn_eval(input, [(self, 0)], bn, relu=False, relu_out=relu)
+            return _mark(y, bn, relu)
+        z = gradacc.library_conv2d(input, self)  # strided: MIOpen
+        return _mark(bn_eval_act(z, bn, relu, inplace=True), bn, relu)
+
 
 class Linear(nn.Linear):
     """``nn.Linear`` (same parameters) whose gradients are accumulated into ``.grad`` by its
@@ -332,6 +394,12 @@ class BatchNormAct2d(nn.BatchNorm2d):
         relu = bool(self.__dict__.get(_RELU, False))
         if input.dim() == 4 and _native_bn_ok(self, input):
             y = bn_act(input, self, relu)
+            if relu:
+                setattr(y, _DONE_RELU, True)
+            return y
+        if type(self) is BatchNormAct2d and not self.training and input.dim() == 4 and \
+                _native_bn_eval_ok(self, input):
+            y = bn_eval_act(input, self, relu)
             if relu:
                 setattr(y, _DONE_RELU, True)
             return y
