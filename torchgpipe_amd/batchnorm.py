@@ -25,6 +25,15 @@ MI355X implementation (fp32 GPU tensors):
   and zeroes them.  ``sum`` / ``sum_squares`` stay registered (and zero) so the
   reference's state-dict keys are unchanged.
 * CPU tensors: the same Chan accumulation in fp64 PyTorch ops (the oracle).
+* The fused Conv-BN ops (``ops/convbn.py``: ``relu_conv_bn``, the grouped op) and the linked
+  layers of ``ops/fusion.py`` take a ``DeferredBatchNorm`` wherever they take a
+  ``BatchNorm2d``.  They run the normalisation themselves and use two calls of this module:
+  :meth:`DeferredBatchNorm.fold_acc` (the accumulator their finalize kernel folds the
+  micro-batch into; ``None`` while recomputing) and :meth:`DeferredBatchNorm.fold_done` (the
+  counters, and the commit after the mini-batch's last micro-batch).  ``forward`` uses the
+  same two calls; it passes through an input that a linked convolution has already
+  normalised with this module, applies a linked ReLU in its native pass, and in eval mode
+  runs the native ``bn_eval_act`` pass where ``nn.BatchNorm2d`` would.
 
 Deliberate fixes over the reference:
 
@@ -51,22 +60,37 @@ TModule = TypeVar('TModule', bound=nn.Module)
 
 
 class _BNTrain(torch.autograd.Function):
-    """Native BatchNorm-train forward/backward; folds statistics into ``acc`` if given."""
+    """Native BatchNorm-train (+ ReLU) forward/backward; folds statistics into ``acc`` if given."""
 
     @staticmethod
     def forward(ctx, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],  # type: ignore[override]
-                acc: Optional[Tensor], eps: float) -> Tensor:
-        y, mean, invstd, sums = _ext.require(x).bn_train_forward(x, weight, bias, acc, eps)
-        ctx.save_for_backward(x, mean, invstd, sums, weight)
+                acc: Optional[Tensor], eps: float, relu: bool = False) -> Tensor:
+        y, mean, invstd, sums = _ext.require(x).bn_train_forward(
+            x, weight, bias, acc, eps, None, None, None, 0.0, relu)
+        # (bias only for the ReLU mask, re-derived from x in the backward)
+        ctx.save_for_backward(x, mean, invstd, sums, weight, bias if relu else None)
+        ctx.relu = relu
         return y
 
     @staticmethod
     def backward(ctx, dy: Tensor):  # type: ignore[override]
-        x, mean, invstd, sums, weight = ctx.saved_tensors
-        dx, dgamma, dbeta = _ext.require(dy).bn_train_backward(dy, x, mean, invstd, sums,
-                                                                weight)
+        x, mean, invstd, sums, weight, bias = ctx.saved_tensors
+        dx, dgamma, dbeta = _ext.require(dy).bn_train_backward(dy.contiguous(), x, mean, invstd,
+                                                                sums, weight, bias, ctx.relu)
         return (dx, dgamma if ctx.needs_input_grad[1] else None,
-                dbeta if ctx.needs_input_grad[2] else None, None, None)
+                dbeta if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+_FUSION = None
+
+
+def _fusion():  # type: ignore[no-untyped-def]
+    """``ops.fusion`` (which imports this module), bound on first use."""
+    global _FUSION
+    if _FUSION is None:
+        from torchgpipe_amd.ops import fusion
+        _FUSION = fusion
+    return _FUSION
 
 
 def _chan_merge_(acc: Tensor, x: Tensor) -> None:
@@ -125,11 +149,23 @@ class DeferredBatchNorm(_BatchNorm):
         return (input.is_cuda and input.dtype == torch.float32
                 and self.running_mean.dtype == torch.float32 and _ext.available())
 
-    def _tracked_one(self, input: Tensor) -> bool:
-        self.counter += input.numel() // input.size(1)
+    def fold_acc(self) -> Optional[Tensor]:
+        """The accumulator the op normalising this micro-batch folds its (count, mean, M2)
+        into -- this module's own forward or a fused Conv-BN op running it -- or ``None``
+        during checkpoint recomputation, which tracks nothing."""
+        return None if is_recomputing() else self.acc
+
+    def fold_done(self, count: int) -> None:
+        """Bookkeeping after an op folded one micro-batch of ``count`` values per channel
+        into :meth:`fold_acc`: commits the running statistics when it was the mini-batch's
+        last.  Nothing happens during recomputation."""
+        if is_recomputing():
+            return
+        self.counter += count
         self.tracked += 1
         target = self.expected_chunks if self.expected_chunks is not None else self.chunks
-        return self.tracked >= target
+        if self.tracked >= target:
+            self._commit()
 
     def _commit(self) -> None:
         self.num_batches_tracked += 1
@@ -153,20 +189,30 @@ class DeferredBatchNorm(_BatchNorm):
         self.tracked = 0
 
     def forward(self, input: Tensor) -> Tensor:  # type: ignore[override]
+        if getattr(input, '_tgpipe_bn_done', None) == id(self):
+            return input  # a linked convolution ran this BatchNorm (ops/fusion.py)
         self._check_input_dim(input)
+        # a ReLU linked after this module (ops.fusion.relink) is applied by the native pass
+        relu = bool(self.__dict__.get('_tgpipe_relu_next', False))
         if not self.training:
+            if input.dim() == 4 and _fusion()._native_bn_eval_ok(self, input):
+                out = _fusion().bn_eval_act(input, self, relu)
+                if relu:
+                    setattr(out, '_tgpipe_relu_done', True)
+                return out
             return F.batch_norm(input, self.running_mean, self.running_var,
                                 self.weight, self.bias, False, 0.0, self.eps)
-        track = not is_recomputing()
+        acc = self.fold_acc()
         if self._native(input):
-            out = _BNTrain.apply(input.contiguous(), self.weight, self.bias,
-                                 self.acc if track else None, float(self.eps))
+            out = _BNTrain.apply(input.contiguous(), self.weight, self.bias, acc,
+                                 float(self.eps), relu)
+            if relu:
+                setattr(out, '_tgpipe_relu_done', True)
         else:
-            if track:
-                _chan_merge_(self.acc, input)
+            if acc is not None:
+                _chan_merge_(acc, input)
             out = F.batch_norm(input, None, None, self.weight, self.bias, True, 0.0, self.eps)
-        if track and self._tracked_one(input):
-            self._commit()
+        self.fold_done(input.numel() // input.size(1))
         return out
 
     @classmethod

@@ -32,6 +32,17 @@ __device__ __forceinline__ void chan_merge(double& na, double& ma, double& m2a, 
   na = n;
 }
 
+// DeferredBatchNorm: fold one micro-batch's channel statistics into the mini-batch
+// accumulators acc [3][c] (count, mean, M2) -- committed once per mini-batch by dbn_commit64.
+__device__ __forceinline__ void acc_fold(double* __restrict__ acc, int64_t c, int64_t ch,
+                                         double na, double ma, double m2a) {
+  double n0 = acc[ch], m0 = acc[c + ch], q0 = acc[2 * c + ch];
+  chan_merge(n0, m0, q0, na, ma, m2a);
+  acc[ch] = n0;
+  acc[c + ch] = m0;
+  acc[2 * c + ch] = q0;
+}
+
 // 32 lanes per channel merge strided subsets of the column-block partials, then a
 // 5-level shuffle tree merges the lanes: ~blocks/32 + 5 dependent fp64 steps instead
 // of `blocks` (AmoebaNet's 56^2 planes at 20 images: 980 blocks).
@@ -102,6 +113,7 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(
   // output channel ch of the statistics / z; with parts (a grouped convolution feeding
   // several BatchNorms) its parameters, running statistics and output come from its part
   int yc = c, ych = ch;
+  double* pacc = nullptr;
   if (parts.count > 0) {
     int pi = 0;
     while (pi + 1 < parts.count && ch >= parts.c_end[pi]) ++pi;
@@ -113,6 +125,7 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(
     rm = parts.rm[pi] ? parts.rm[pi] - begin : nullptr;
     rv = parts.rv[pi] ? parts.rv[pi] - begin : nullptr;
     tracked = ych == 0 ? parts.tracked[pi] : nullptr;
+    pacc = parts.acc[pi];
     y = parts.y[pi];
   }
   double na = 0.0, ma = 0.0, m2a = 0.0;
@@ -155,12 +168,10 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(
       }
       mean[ch] = mu;
       invstd[ch] = is;
-      if (acc != nullptr) {  // DeferredBatchNorm mini-batch accumulators (dbn_commit64)
-        double n0 = acc[ch], m0 = acc[c + ch], q0 = acc[2 * c + ch];
-        chan_merge(n0, m0, q0, na, ma, m2a);
-        acc[ch] = n0;
-        acc[c + ch] = m0;
-        acc[2 * c + ch] = q0;
+      if (parts.count > 0) {  // the part's own accumulator [3][yc], part-local channel
+        if (pacc != nullptr) acc_fold(pacc, yc, ych, na, ma, m2a);
+      } else if (acc != nullptr) {  // DeferredBatchNorm mini-batch accumulators (dbn_commit64)
+        acc_fold(acc, c, ch, na, ma, m2a);
       }
       if (rm != nullptr) {
         const double unbiased = na > 1.0 ? m2a / (na - 1.0) : var;
@@ -254,6 +265,7 @@ __global__ __launch_bounds__(256) void split_bn_small_kernel(
   const int ch = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int yc = c, ych = ch;
+  double* pacc = nullptr;
   if (parts.count > 0) {  // (as bn_finalize_apply_kernel)
     int pi = 0;
     while (pi + 1 < parts.count && ch >= parts.c_end[pi]) ++pi;
@@ -265,6 +277,7 @@ __global__ __launch_bounds__(256) void split_bn_small_kernel(
     rm = parts.rm[pi] ? parts.rm[pi] - begin : nullptr;
     rv = parts.rv[pi] ? parts.rv[pi] - begin : nullptr;
     tracked = ych == 0 ? parts.tracked[pi] : nullptr;
+    pacc = parts.acc[pi];
     y = parts.y[pi];
   }
   const int total = n * s;
@@ -324,12 +337,10 @@ __global__ __launch_bounds__(256) void split_bn_small_kernel(
     }
     mean[ch] = mu;
     invstd[ch] = is;
-    if (acc != nullptr) {
-      double n0 = acc[ch], m0 = acc[c + ch], q0 = acc[2 * c + ch];
-      chan_merge(n0, m0, q0, na, ma, m2a);
-      acc[ch] = n0;
-      acc[c + ch] = m0;
-      acc[2 * c + ch] = q0;
+    if (parts.count > 0) {  // (as bn_finalize_apply_kernel)
+      if (pacc != nullptr) acc_fold(pacc, yc, ych, na, ma, m2a);
+    } else if (acc != nullptr) {
+      acc_fold(acc, c, ch, na, ma, m2a);
     }
     if (rm != nullptr) {
       const double unbiased = na > 1.0 ? m2a / (na - 1.0) : var;

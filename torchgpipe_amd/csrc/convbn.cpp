@@ -565,6 +565,15 @@ const float* opt_ptr(const c10::optional<at::Tensor>& t, const char* name, const
   return t->data_ptr<float>();
 }
 
+// DeferredBatchNorm's mini-batch accumulator (count, mean, M2), or null when not given.
+double* acc_ptr(const c10::optional<at::Tensor>& acc, const at::Tensor& like, int64_t c) {
+  if (!acc.has_value() || !acc->defined()) return nullptr;
+  TORCH_CHECK(acc->device() == like.device() && acc->scalar_type() == at::kDouble &&
+                  acc->is_contiguous() && acc->numel() == 3 * c,
+              "acc must be a contiguous float64 [3][C] tensor on the input's device");
+  return acc->data_ptr<double>();
+}
+
 struct Parts {
   std::vector<ConvGemmGeo> geo;
   int64_t co_total = 0, ho = 0, wo = 0;
@@ -649,12 +658,15 @@ std::vector<at::Tensor> convbn_forward(const at::Tensor& x_in, at::TensorList we
                                        const c10::optional<at::Tensor>& running_var,
                                        const c10::optional<at::Tensor>& num_batches_tracked,
                                        double momentum, double eps,
-                                       const c10::optional<at::Tensor>& add, bool relu_out) {
+                                       const c10::optional<at::Tensor>& add, bool relu_out,
+                                       const c10::optional<at::Tensor>& acc) {
   auto x = x_in.contiguous();
   check_f32(x, "x", x);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Parts p = make_parts(x, weights, geo, relu);
   const int64_t n = x.size(0), c = p.co_total, s = p.ho * p.wo, cols = n * s;
+  // DeferredBatchNorm: every finalize route below folds the micro-batch into `acc`
+  double* const accp = acc_ptr(acc, x, c);
   const auto stream = cur_stream(x);
   auto z = at::empty({n, c, p.ho, p.wo}, x.options());
   std::vector<ConvGemmPlan> plans;
@@ -714,7 +726,7 @@ std::vector<at::Tensor> convbn_forward(const at::Tensor& x_in, at::TensorList we
     launch_split_bn_small(ws.data_ptr<float>(), pl.splits, c * cols, z.data_ptr<float>(), n, c,
                           s, static_cast<float>(eps), momentum, mean.data_ptr<float>(),
                           invstd.data_ptr<float>(), const_cast<float*>(rm),
-                          const_cast<float*>(rv), tracked, nullptr, sums.data_ptr<float>(), ga,
+                          const_cast<float*>(rv), tracked, accp, sums.data_ptr<float>(), ga,
                           be, ad, y.data_ptr<float>(), stream, relu_out);
     return {y, z, mean, invstd, sums};
   }
@@ -737,7 +749,7 @@ std::vector<at::Tensor> convbn_forward(const at::Tensor& x_in, at::TensorList we
   launch_bn_finalize_apply(part0, part1, blocks, width, n,
                            c, s, static_cast<float>(eps), momentum, mean.data_ptr<float>(),
                            invstd.data_ptr<float>(), const_cast<float*>(rm),
-                           const_cast<float*>(rv), tracked, nullptr, sums.data_ptr<float>(),
+                           const_cast<float*>(rv), tracked, accp, sums.data_ptr<float>(),
                            z.data_ptr<float>(), ga, be, ad, y.data_ptr<float>(), stream, relu_out);
   return {y, z, mean, invstd, sums};
 }
@@ -1218,7 +1230,8 @@ std::vector<at::Tensor> convbn_group_forward(
     const c10::List<c10::optional<at::Tensor>>& betas,
     const c10::List<c10::optional<at::Tensor>>& running_means,
     const c10::List<c10::optional<at::Tensor>>& running_vars,
-    const c10::List<c10::optional<at::Tensor>>& tracked, double momentum, double eps) {
+    const c10::List<c10::optional<at::Tensor>>& tracked, double momentum, double eps,
+    const c10::optional<c10::List<c10::optional<at::Tensor>>>& accs) {
   auto x = x_in.contiguous();
   check_f32(x, "x", x);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -1229,8 +1242,12 @@ std::vector<at::Tensor> convbn_group_forward(
   TORCH_CHECK(running_means.size() == channels.size() && running_vars.size() == channels.size() &&
                   tracked.size() == channels.size(),
               "one running_mean / running_var / num_batches_tracked per grouped operation");
+  TORCH_CHECK(!accs.has_value() || accs->size() == channels.size(),
+              "one accumulator (or none) per grouped operation");
   std::vector<at::Tensor> out;
   for (size_t i = 0; i < channels.size(); ++i) {
+    // DeferredBatchNorm: each operation folds into its own [3][C_i] accumulator
+    if (accs.has_value()) pt.acc[i] = acc_ptr(accs->get(i), x, channels[i]);
     pt.rm[i] = const_cast<float*>(opt_ptr(running_means.get(i), "running_mean", x, channels[i]));
     pt.rv[i] = const_cast<float*>(opt_ptr(running_vars.get(i), "running_var", x, channels[i]));
     TORCH_CHECK((pt.rm[i] == nullptr) == (pt.rv[i] == nullptr),
@@ -1586,13 +1603,7 @@ std::vector<at::Tensor> bn_train_forward(const at::Tensor& x_in,
   auto mean = st.mean, invstd = st.invstd;
   auto y = at::empty_like(x);
   if (x.numel() == 0) return {y, mean.zero_(), invstd.fill_(1.f), at::zeros({2, c}, x.options())};
-  double* accp = nullptr;
-  if (acc.has_value() && acc->defined()) {
-    TORCH_CHECK(acc->device() == x.device() && acc->scalar_type() == at::kDouble &&
-                    acc->is_contiguous() && acc->numel() == 3 * c,
-                "acc must be a contiguous float64 [3][C] tensor on the input's device");
-    accp = acc->data_ptr<double>();
-  }
+  double* const accp = acc_ptr(acc, x, c);
   const float* rm = opt_ptr(running_mean, "running_mean", x, c);
   const float* rv = opt_ptr(running_var, "running_var", x, c);
   TORCH_CHECK((rm == nullptr) == (rv == nullptr), "running_mean and running_var go together");
@@ -1828,7 +1839,7 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
   m.def("convbn_forward(Tensor x, Tensor[] weights, int[] geo, bool relu, Tensor? gamma, "
         "Tensor? beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
         "Tensor(c!)? num_batches_tracked, float momentum, float eps, Tensor? add, "
-        "bool relu_out=False) -> Tensor[]");
+        "bool relu_out=False, Tensor(d!)? acc=None) -> Tensor[]");
   m.def("convbn_eval_forward(Tensor x, Tensor[] weights, int[] geo, bool relu, Tensor? gamma, "
         "Tensor? beta, Tensor running_mean, Tensor running_var, float eps, Tensor? add, "
         "bool relu_out=False) -> Tensor");
@@ -1841,7 +1852,7 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
         "Tensor? y_mask=None, Tensor(b!)? dy_masked=None) -> Tensor[]");
   m.def("convbn_group_forward(Tensor x, Tensor w_cat, int[] geo, bool relu, int[] channels, "
         "Tensor?[] gammas, Tensor?[] betas, Tensor?[] running_means, Tensor?[] running_vars, "
-        "Tensor?[] tracked, float momentum, float eps) -> Tensor[]");
+        "Tensor?[] tracked, float momentum, float eps, Tensor?[]? accs=None) -> Tensor[]");
   m.def("convbn_group_backward(Tensor?[] dys, Tensor x, Tensor z, Tensor mean, Tensor invstd, "
         "Tensor[] weights, Tensor w_cat_t, int[] geo, bool relu, bool need_dx, int[] channels, "
         "Tensor?[] gammas, Tensor?[] accum, Tensor?[] slabs, int[] slab_first) -> Tensor[]");

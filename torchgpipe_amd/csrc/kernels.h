@@ -312,6 +312,9 @@ void launch_bn_eval_act(const float* x, const float* gamma, const float* beta,
 // [c_end[p-1], c_end[p]) of z / mean / invstd and has its own parameters, running
 // statistics and output y_p [n][c_p][s] (forward) / gradient dy_p (image stride dy_img[p];
 // null = no gradient) and parameter gradients (backward).  count = 0: not grouped.
+// acc[p] (may be null): part p's own DeferredBatchNorm accumulator, fp64 [3][c_p], folded by
+// the forward's finalize with the part-local channel (the launchers' single `acc` is the
+// ungrouped BatchNorm's and is not read when count > 0).
 constexpr int kBnPartsMax = 3;
 struct BnParts {
   int count;
@@ -321,6 +324,7 @@ struct BnParts {
   float* rm[kBnPartsMax];
   float* rv[kBnPartsMax];
   int64_t* tracked[kBnPartsMax];
+  double* acc[kBnPartsMax];
   float* y[kBnPartsMax];
   const float* dy[kBnPartsMax];
   int64_t dy_img[kBnPartsMax];

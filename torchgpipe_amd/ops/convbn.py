@@ -20,6 +20,14 @@ the reference's children (``ReLU``, ``Conv2d``, ``BatchNorm2d`` …), so the
 state-dict keys are unchanged; they fall back to the eager modules on CPU, for
 non-fp32 tensors or unsupported convolutions.
 
+``DeferredBatchNorm`` (``deferred_batch_norm=True``) is taken wherever a ``BatchNorm2d`` is,
+in training and in evaluation: the op normalises the micro-batch with its own statistics as
+always, passes no running buffers, and its finalize -- whichever route the plan takes --
+Chan-merges the micro-batch's (count, mean, M2) into the module's fp64 accumulator
+(``convbn_forward``'s ``acc``; one accumulator per operation of the grouped op).  The
+module's ``fold_done`` then commits the running statistics after the mini-batch's last
+micro-batch; nothing is tracked during checkpoint recomputation.
+
 Evaluation (``model.eval()``) has its own forward-only op, :func:`conv_bn_eval`: an
 eval-mode BatchNorm is a per-channel scale and shift, folded from the running
 statistics inside the implicit GEMM's store loop together with the node sum and the
@@ -27,9 +35,9 @@ output ReLU -- one launch per triplet (a split-K plan: the GEMM and its reductio
 statistics, no saved ``z``, the running buffers untouched.  The remaining eager cases
 in eval: anything that needs a gradient while gradients are enabled (there is no
 backward through the eval op, so frozen-BatchNorm fine-tuning runs eagerly), a
-BatchNorm without running statistics (it normalises with batch statistics),
-``DeferredBatchNorm``, and the grouped three-way op (:func:`group_relu_conv_bn`; each of
-its triplets takes the single-op eval path instead).  The Winograd 3×3 path applies
+BatchNorm without running statistics (it normalises with batch statistics), and the
+grouped three-way op (:func:`group_relu_conv_bn`; each of its triplets takes the single-op
+eval path instead).  The Winograd 3×3 path applies
 the BatchNorm as a separate in-place pass (``ops.fusion.bn_eval_act``) rather than in its
 output transform.
 """
@@ -41,6 +49,7 @@ import torch
 from torch import Tensor, nn
 import torch.nn.functional as F
 
+from torchgpipe_amd.batchnorm import DeferredBatchNorm
 from torchgpipe_amd.ops import _ext, gradacc
 from torchgpipe_amd.ops.conv import _TransformCache
 
@@ -80,9 +89,18 @@ def _geo(conv: nn.Conv2d, offset: int = 0) -> List[int]:
     return [kh, kw, sh, sw, ph, pw, offset, offset]
 
 
+# the BatchNorms the fused ops run: nn.BatchNorm2d, and DeferredBatchNorm on a 4-D input
+_BN_TYPES = (nn.BatchNorm2d, DeferredBatchNorm)
+
+
 def _bn_ok(bn: nn.Module, x: Tensor) -> bool:
-    return (isinstance(bn, nn.BatchNorm2d) and bn.training and x.is_cuda
-            and x.dtype == torch.float32 and x.dim() == 4
+    if not (bn.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+        return False
+    if isinstance(bn, DeferredBatchNorm):
+        # micro-batch statistics folded into its fp64 accumulator by the op's finalize; any
+        # momentum (None too): the factor is applied at the commit (DeferredBatchNorm._commit)
+        return bn.running_mean.dtype == torch.float32 and bn.acc.device == x.device
+    return (isinstance(bn, nn.BatchNorm2d)
             and (bn.momentum is not None or not bn.track_running_stats))
 
 
@@ -95,7 +113,7 @@ def _bn_eval_ok(bn: nn.Module, x: Tensor, add: Optional[Tensor] = None) -> bool:
     """An eval-mode BatchNorm2d the native inference kernels take: fp32 NCHW on the GPU,
     normalising with its running statistics, and nothing that needs a gradient (the eval
     ops are forward-only)."""
-    return (_ENABLED and isinstance(bn, nn.BatchNorm2d) and not bn.training and x.is_cuda
+    return (_ENABLED and isinstance(bn, _BN_TYPES) and not bn.training and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4
             and bn.track_running_stats and bn.running_mean is not None
             and bn.running_var is not None
@@ -178,13 +196,21 @@ class _ConvBN(torch.autograd.Function):
                                                                             Optional[GradSink]],
                 *weights: Tensor) -> Tensor:
         ops = _ext.require(x)
-        track = bn.track_running_stats and bn.running_mean is not None
-        y, z, mean, invstd, sums = ops.convbn_forward(
-            x, list(weights), geo, relu, gamma, beta,
-            bn.running_mean if track else None, bn.running_var if track else None,
-            bn.num_batches_tracked if track else None,
-            float(bn.momentum) if bn.momentum is not None else 0.0, float(bn.eps), add,
-            relu_out)
+        if isinstance(bn, DeferredBatchNorm):
+            # the running buffers wait for the mini-batch's commit: the finalize folds this
+            # micro-batch into the module's accumulator instead (none while recomputing)
+            y, z, mean, invstd, sums = ops.convbn_forward(
+                x, list(weights), geo, relu, gamma, beta, None, None, None, 0.0,
+                float(bn.eps), add, relu_out, bn.fold_acc())
+            bn.fold_done(z.numel() // z.size(1))
+        else:
+            track = bn.track_running_stats and bn.running_mean is not None
+            y, z, mean, invstd, sums = ops.convbn_forward(
+                x, list(weights), geo, relu, gamma, beta,
+                bn.running_mean if track else None, bn.running_var if track else None,
+                bn.num_batches_tracked if track else None,
+                float(bn.momentum) if bn.momentum is not None else 0.0, float(bn.eps), add,
+                relu_out)
         # (beta only for the ReLU mask of relu_out, re-derived from z in the backward; with a
         # node sum the mask comes from the saved output instead: relu(bn(z) + add))
         out_mask = relu_out and add is not None
@@ -363,7 +389,7 @@ def fused_triplets(seq: nn.Sequential) -> Optional[List[Tuple[bool, nn.Conv2d, n
         relu = isinstance(mods[i], nn.ReLU)
         j = i + 1 if relu else i
         if j + 1 >= len(mods) or not isinstance(mods[j], nn.Conv2d) or \
-                not isinstance(mods[j + 1], nn.BatchNorm2d):
+                not isinstance(mods[j + 1], _BN_TYPES):
             return None
         out.append((relu, mods[j], mods[j + 1]))
         i = j + 2
@@ -492,13 +518,23 @@ class _GroupConvBN(torch.autograd.Function):
         gammas, betas = list(params[n_ops:2 * n_ops]), list(params[2 * n_ops:])
         w_cat, _ = cache.get(weights)
         channels = [w.shape[0] for w in weights]
-        track = [bn.track_running_stats and bn.running_mean is not None for bn in bns]
-        outs = _ext.require(x).convbn_group_forward(
-            x, w_cat, [1, 1, 1, 1, 0, 0, 0, 0], True, channels, gammas, betas,
-            [bn.running_mean if t else None for bn, t in zip(bns, track)],
-            [bn.running_var if t else None for bn, t in zip(bns, track)],
-            [bn.num_batches_tracked if t else None for bn, t in zip(bns, track)],
-            float(bns[0].momentum), float(bns[0].eps))
+        if isinstance(bns[0], DeferredBatchNorm):
+            # (groupable: all of them are) each operation's finalize folds into its own
+            # accumulator; the running buffers wait for the commit
+            none: List[Optional[Tensor]] = [None] * n_ops
+            outs = _ext.require(x).convbn_group_forward(
+                x, w_cat, [1, 1, 1, 1, 0, 0, 0, 0], True, channels, gammas, betas,
+                none, none, none, 0.0, float(bns[0].eps), [bn.fold_acc() for bn in bns])
+            for bn in bns:
+                bn.fold_done(x.numel() // x.size(1))
+        else:
+            track = [bn.track_running_stats and bn.running_mean is not None for bn in bns]
+            outs = _ext.require(x).convbn_group_forward(
+                x, w_cat, [1, 1, 1, 1, 0, 0, 0, 0], True, channels, gammas, betas,
+                [bn.running_mean if t else None for bn, t in zip(bns, track)],
+                [bn.running_var if t else None for bn, t in zip(bns, track)],
+                [bn.num_batches_tracked if t else None for bn, t in zip(bns, track)],
+                float(bns[0].momentum), float(bns[0].eps))
         ys, (z, mean, invstd) = outs[:n_ops], outs[n_ops:]
         ctx.save_for_backward(x, z, mean, invstd, *weights, *gammas)
         ctx.params = tuple(params)
@@ -551,12 +587,19 @@ class _GroupConvBN(torch.autograd.Function):
 
 def groupable(x: Tensor, triplets: Sequence[Tuple[bool, nn.Conv2d, nn.BatchNorm2d]]) -> bool:
     """Whether :func:`group_relu_conv_bn` takes these (relu, conv, bn) triplets: ReLU ->
-    plain 1x1 convolutions of ``x`` -> BatchNorms with one momentum / eps, the grouped
+    plain 1x1 convolutions of ``x`` -> BatchNorms of one kind (all ``BatchNorm2d`` or all
+    ``DeferredBatchNorm`` with the same ``chunks``) with one momentum / eps, the grouped
     BatchNorm backward's channel size limit, and the fused-op conditions."""
     if not _GROUP_ENABLED or not 2 <= len(triplets) <= 3 or x.dim() != 4:
         return False
     bn0 = triplets[0][2]
+    deferred = isinstance(bn0, DeferredBatchNorm)
     for relu, conv, bn in triplets:
+        # one kind of BatchNorm, and deferred ones committing after the same micro-batch
+        if isinstance(bn, DeferredBatchNorm) != deferred or \
+                (deferred and (bn.chunks, bn.expected_chunks) !=
+                 (bn0.chunks, bn0.expected_chunks)):
+            return False
         if not relu or tuple(conv.kernel_size) != (1, 1) or tuple(conv.stride) != (1, 1) or \
                 tuple(conv.padding) != (0, 0) or not fusable(x, [conv], bn) or \
                 bn.momentum != bn0.momentum or bn.eps != bn0.eps or \

@@ -30,16 +30,21 @@ one native op needs the layers to cooperate:
 Links are only made between consecutive layers of one ``nn.Sequential`` -- one pipeline
 partition -- so a balance that separates a convolution from its BatchNorm leaves both
 running on their own.  ``GPipe`` and ``PipelineStage`` call :func:`relink` on every
-partition after splitting (and after DeferredBatchNorm conversion, whose BatchNorms are
-not linked).  On the CPU or for non-fp32 tensors every layer runs its plain PyTorch forward.
+partition after splitting and after DeferredBatchNorm conversion: a ``DeferredBatchNorm``
+stands where the :class:`BatchNormAct2d` stood and is linked the same way -- to the
+convolution before it, the ReLU after it and the residual join.  Every branch above then
+runs unchanged, except that the op's finalize folds the micro-batch statistics into the
+module's fp64 accumulator instead of updating the running buffers, and the module's
+bookkeeping (``fold_acc`` / ``fold_done``) commits them once per mini-batch.  On the CPU or
+for non-fp32 tensors every layer runs its plain PyTorch forward.
 
 Evaluation (``model.eval()`` with nothing needing a gradient) takes the same branches on
 forward-only ops: the pointwise and ``STRIDED_FUSED`` convolutions and the residual join
 run ``ops.convbn.conv_bn_eval`` (the BatchNorm folded from its running statistics into the
 GEMM's store loop, with the identity add and the ReLU: one launch), the Winograd and the
 other strided convolutions are followed by :func:`bn_eval_act` in place on their output,
-and an unlinked :class:`BatchNormAct2d` runs :func:`bn_eval_act` with its linked ReLU.  A
-BatchNorm without running statistics, ``DeferredBatchNorm``, and an eval forward that needs
+and an unlinked :class:`BatchNormAct2d` (or ``DeferredBatchNorm``) runs :func:`bn_eval_act`
+with its linked ReLU.  A BatchNorm without running statistics and an eval forward that needs
 gradients stay on the plain PyTorch forward.
 """
 import os
@@ -49,6 +54,7 @@ import torch
 from torch import Tensor, nn
 import torch.nn.functional as F
 
+from torchgpipe_amd.batchnorm import DeferredBatchNorm
 from torchgpipe_amd.ops import _ext, convbn, gradacc
 from torchgpipe_amd.ops.conv import WinogradConv2d, conv_with_bn_stats, wino_eligible
 from torchgpipe_amd.ops.convbn import (GradSink, _bn_eval_ok, _bn_ok, fusable, gemm_conv2d,
@@ -57,8 +63,8 @@ from torchgpipe_amd.ops.convbn import (GradSink, _bn_eval_ok, _bn_ok, fusable, g
 __all__ = ['ConvBN2d', 'BatchNormAct2d', 'ReLU', 'Linear', 'relink', 'bn_act', 'add_relu',
            'pending_join', 'bn_eval_act']
 
-_LINK = '_tgpipe_link'       # ConvBN2d -> (BatchNormAct2d, relu?)
-_RELU = '_tgpipe_relu_next'  # BatchNormAct2d -> a linked ReLU follows
+_LINK = '_tgpipe_link'       # ConvBN2d -> (BatchNormAct2d / DeferredBatchNorm, relu?, join)
+_RELU = '_tgpipe_relu_next'  # BatchNormAct2d / DeferredBatchNorm -> a linked ReLU follows
 _DONE_BN = '_tgpipe_bn_done'    # tensor mark: id() of the BatchNorm already applied
 _DONE_RELU = '_tgpipe_relu_done'  # tensor mark: the ReLU after it too
 _PENDING = '_tgpipe_pending'  # tensor mark: (conv, bn) left for the residual join to run
@@ -72,20 +78,28 @@ BN_GRAD_ACCUM = os.environ.get('TGPIPE_BN_GRAD_ACCUM', '1') != '0'
 
 
 class _BNAct(torch.autograd.Function):
-    """Training-mode BatchNorm2d (batch statistics, running-stat EMA) + optional ReLU on the
-    native kernels (``csrc/batchnorm.hip``): statistics pass, finalize + normalise (+ ReLU)."""
+    """Training-mode BatchNorm2d (batch statistics, running-stat EMA -- or, for a
+    DeferredBatchNorm, the fold into its mini-batch accumulator) + optional ReLU on the native
+    kernels (``csrc/batchnorm.hip``): statistics pass, finalize + normalise (+ ReLU)."""
 
     @staticmethod
     def forward(ctx, x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor],  # type: ignore[override]
                 bn: nn.BatchNorm2d, relu: bool, part: Optional[Tensor] = None,
                 part_images: int = 0) -> Tensor:
-        track = bn.track_running_stats and bn.running_mean is not None
         # part: x's statistics partials from its producer (ops/conv.py conv_with_bn_stats)
-        y, mean, invstd, sums = _ext.require(x).bn_train_forward(
-            x, gamma, beta, None, float(bn.eps),
-            bn.running_mean if track else None, bn.running_var if track else None,
-            bn.num_batches_tracked if track else None,
-            float(bn.momentum) if track else 0.0, relu, part, part_images)
+        if isinstance(bn, DeferredBatchNorm):
+            # folded into the module's accumulator; the running buffers wait for its commit
+            y, mean, invstd, sums = _ext.require(x).bn_train_forward(
+                x, gamma, beta, bn.fold_acc(), float(bn.eps), None, None, None, 0.0, relu,
+                part, part_images)
+            bn.fold_done(x.numel() // x.size(1))
+        else:
+            track = bn.track_running_stats and bn.running_mean is not None
+            y, mean, invstd, sums = _ext.require(x).bn_train_forward(
+                x, gamma, beta, None, float(bn.eps),
+                bn.running_mean if track else None, bn.running_var if track else None,
+                bn.num_batches_tracked if track else None,
+                float(bn.momentum) if track else 0.0, relu, part, part_images)
         ctx.save_for_backward(x, mean, invstd, sums, gamma, beta)
         ctx.relu = relu
         ctx.params = (bn.weight, bn.bias)
@@ -193,7 +207,10 @@ def pending_join(x: Tensor, join: nn.Module, identity: Tensor) -> Optional[Tenso
         elif convbn.eval_fusable(x, [conv], bn):
             y = F.relu(convbn.conv_bn_eval(x, [(conv, 0)], bn, relu=False) + identity)
         else:
-            y = F.relu(nn.BatchNorm2d.forward(bn, nn.Conv2d.forward(conv, x)) + identity)
+            # (the plain eval normalisation, whichever kind of BatchNorm ``bn`` is)
+            z = F.batch_norm(nn.Conv2d.forward(conv, x), bn.running_mean, bn.running_var,
+                             bn.weight, bn.bias, False, 0.0, bn.eps)
+            y = F.relu(z + identity)
     elif identity.shape != (n, conv.out_channels, h, w) or identity.dtype != x.dtype:
         y = relu_conv_bn(x, [(conv, 0)], bn, relu=False) + identity
         y = F.relu(y)
@@ -415,9 +432,15 @@ class ReLU(nn.ReLU):
         return F.relu(input, inplace=self.inplace)
 
 
+# the BatchNorm layers relink links: BatchNormAct2d and what DeferredBatchNorm conversion
+# makes of it (both pass a marked input through and apply a linked ReLU themselves)
+_LINKED_BN = (BatchNormAct2d, DeferredBatchNorm)
+
+
 def relink(module: nn.Module) -> int:
     """(Re)link every ``ConvBN2d, BatchNormAct2d[, ReLU]`` run of consecutive children of
-    each ``nn.Sequential`` in ``module``; earlier links inside ``module`` are dropped first.
+    each ``nn.Sequential`` in ``module`` (a ``DeferredBatchNorm`` in the BatchNorm's place is
+    linked the same way); earlier links inside ``module`` are dropped first.
     Returns the number of convolutions linked."""
     for m in module.modules():
         m.__dict__.pop(_LINK, None)
@@ -429,11 +452,11 @@ def relink(module: nn.Module) -> int:
         kids = list(seq.children())
         for i, m in enumerate(kids):
             inner = getattr(m, 'module', m)  # (a @skippable layer wraps the real module)
-            if (type(m) is BatchNormAct2d or getattr(inner, 'fuses_relu', False)) and \
+            if (type(m) in _LINKED_BN or getattr(inner, 'fuses_relu', False)) and \
                     i + 1 < len(kids) and type(kids[i + 1]) is ReLU:
                 inner.__dict__[_RELU] = True
             if not isinstance(m, ConvBN2d) or i + 1 >= len(kids) or \
-                    type(kids[i + 1]) is not BatchNormAct2d:
+                    type(kids[i + 1]) not in _LINKED_BN:
                 continue
             relu = i + 2 < len(kids) and type(kids[i + 2]) is ReLU
             join = None
