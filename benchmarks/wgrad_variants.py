@@ -1,6 +1,7 @@
 """Time the Winograd weight-gradient kernels (F(2x2) variants 0 / 2, F(4x4)) against MIOpen's wrw.
 
     python benchmarks/wgrad_variants.py --out gpurun_out/wgrad_variants.json
+    python benchmarks/wgrad_variants.py --unet --ab 0 3 --repeats 5   # F(4x4), interleaved
 """
 import argparse
 import json
@@ -19,6 +20,11 @@ SHAPES = [  # N, C, K, H
     (40, 128, 128, 96), (40, 512, 512, 24),
     (3, 70, 130, 13),
 ]
+
+# U-Net(5,64) layers whose weight gradient runs the fused F(4x4) kernel (micro-batch 40)
+UNET_SHAPES = [(40, 64, 64, 192), (40, 128, 64, 192), (40, 128, 32, 192), (40, 32, 32, 192),
+               (40, 64, 128, 96), (40, 128, 128, 96), (40, 256, 64, 96), (40, 256, 64, 48),
+               (40, 64, 64, 48), (40, 512, 128, 24), (40, 128, 128, 24)]
 
 
 def timed(fn, iters):  # type: ignore[no-untyped-def]
@@ -40,14 +46,38 @@ def main() -> None:
     p.add_argument('--shape', type=int, nargs=4, action='append', default=None,
                    help='N C K H (repeatable; default: the built-in table)')
     p.add_argument('--all-f4', action='store_true', help='time F(4x4) below 8x8 planes too')
+    p.add_argument('--unet', action='store_true', help='the U-Net(5,64) micro-batch-40 table')
+    p.add_argument('--ab', type=int, nargs='+', default=None,
+                   help='wino4_wgrad variants to time interleaved (with --repeats), nothing else')
+    p.add_argument('--repeats', type=int, default=5)
     a = p.parse_args()
     ops = _ext.require()
     rows = []
-    for n, c, k, h in (a.shape or SHAPES):
+    for n, c, k, h in (a.shape or (UNET_SHAPES if a.unet else SHAPES)):
         torch.manual_seed(0)
         x = torch.randn(n, c, h, h, device='cuda')
         dy = torch.randn(n, k, h, h, device='cuda')
         w0 = torch.zeros(k, c, 3, 3, device='cuda')
+        if a.ab:
+            # one warm-up of each, then the variants in turn, --repeats times: median and
+            # (min, max) of each
+            row = {'shape': [n, c, k, h]}
+            base = ops.wino4_wgrad(x, dy, 0, a.ab[0])
+            times = {v: [] for v in a.ab}
+            for v in a.ab:
+                timed(lambda: ops.wino4_wgrad(x, dy, 0, v), 1)
+            for _ in range(a.repeats):
+                for v in a.ab:
+                    times[v].append(timed(lambda: ops.wino4_wgrad(x, dy, 0, v), a.iters))
+            for v, ts in times.items():
+                ts.sort()
+                row[f'f4v{v}'] = {'ms': round(ts[len(ts) // 2], 4), 'min': round(ts[0], 4),
+                                  'max': round(ts[-1], 4),
+                                  'equal_to_first': bool(torch.equal(
+                                      ops.wino4_wgrad(x, dy, 0, v), base))}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            continue
 
         def miopen():  # type: ignore[no-untyped-def]
             return torch.ops.aten.convolution_backward(dy, x, w0, None, [1, 1], [1, 1], [1, 1],
@@ -65,7 +95,7 @@ def main() -> None:
             row[f'v{v}'] = {'ms': round(ms, 4), 'direct_tflops': round(flops / ms / 1e9, 1),
                             'rel_err': err}
         if h >= 8 or a.all_f4:
-            for name, var in (('f4', 0), ('f4nf', 1), ('f4emu', 2)):
+            for name, var in (('f4', 0), ('f4nf', 1), ('f4emu', 2), ('f4rows', 3)):
                 got = ops.wino4_wgrad(x, dy, 0, var)
                 err = ((got.double() - ref).abs().max() / ref.abs().max()).item()
                 ms = timed(lambda: ops.wino4_wgrad(x, dy, 0, var), a.iters)

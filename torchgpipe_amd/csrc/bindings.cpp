@@ -222,8 +222,8 @@ at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
   auto y = at::empty({n, out_channels, h, w}, x.options());
   if (y.numel() == 0) return y;
   TORCH_CHECK(variant == -1 || (variant >= 4 && variant <= 15 && variant != 11 && variant != 13) ||
-                  variant == 18,
-              "variant must be -1, 4-10, 12, 14, 15 or 18");
+                  variant == 16 || variant == 17 || variant == 18 || (variant >= 20 && variant <= 22),
+              "variant must be -1, 4-10, 12, 14-18 or 20-22");
   const WinoPlan plan = wino4_plan(n, r, h, w, out_channels, static_cast<int>(variant),
                                    static_cast<int>(splits));
   at::Tensor ws;
@@ -302,8 +302,9 @@ at::Tensor wino4_wgrad(const at::Tensor& x_in, const at::Tensor& dy_in, int64_t 
   TORCH_CHECK(wino4_wgrad_supported(n, c, k, h, w),
               "input too large for the F(4x4) weight-gradient kernel (needs < 1 GiB); "
               "use wino_wgrad");
-  TORCH_CHECK(variant >= 0 && variant <= 2,
-              "variant must be 0 (fused), 1 (non-fused) or 2 (split-bf16 batched GEMM)");
+  TORCH_CHECK(variant >= 0 && variant <= 3,
+              "variant must be 0 (fused), 1 (non-fused), 2 (split-bf16 batched GEMM) or 3 (fused, "
+              "x rows through LDS)");
   // every split owns >= 1 step (of 4 tiles; of 16 for the split-bf16 GEMM)
   const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
   const int64_t steps = variant == 2 ? (tiles + 15) / 16 : (tiles + 3) / 4;

@@ -29,7 +29,11 @@
 //            f4_gemm_kernel copies both operands by LDS-DMA               <- >= 512 channels
 //    8-10    timing ablations of the fused patch staging (wrong results)
 //   12       6 with 16-byte patch-row loads
-// Weight gradient: f4_wgrad_kernel (fused) and f4_wg_vx/_mdy + f4_wgrad_gemm (non-fused).
+//   16       6 with the raw input rows staged through LDS (W % 4 == 0; else runs as 6)
+//   17       7 with the same ring (measured slower than 7; not selected)
+//   20-22    timing ablations of variant 16 (wrong results)
+// Weight gradient: f4_wgrad_kernel (fused; f4_wgrad_rows_kernel: the same with the x rows
+// staged through LDS, wino4_wgrad variant 3) and f4_wg_vx/_mdy + f4_wgrad_gemm (non-fused).
 //
 // Padding taps (image borders, tiles past the end) are raw buffer loads with an
 // out-of-range offset: the hardware returns 0, so no select sits between a load and
@@ -661,6 +665,262 @@ __global__ __launch_bounds__(512, 1) void f4_conv_ring_kernel(
                       H, W, O, o0 + wo * 16 + 4 * (lane >> 4));
 }
 
+// Variant 16: variant 6 with the raw input rows of a step staged through LDS.  Variant 6's
+// patch waves fetch each 6x6 patch tap by tap (36 dword requests per lane and step, ~290
+// 128-byte line requests per workgroup), and the per-CU address / tag work of those
+// requests -- not their latency -- is what the step pays for (profiles/KERNELS.md).  The 32
+// tiles of a workgroup are consecutive, so their patches are a few contiguous row
+// segments: one segment per run of tiles in one tile row, 6 input rows from the 16-byte
+// chunk left of the first tile to the chunk right of the last.  The slab waves fetch these
+// chunks (aligned 16-byte buffer loads, <= kPer per lane and step) into a two-slot LDS ring
+// beside the two [U | V] buffers, and the patch waves read their taps from it (one dword,
+// one 16-byte and one dword LDS read per patch row) into the unchanged transform.
+//
+//   slot = [4 c][6 rows][kRS chunks]; chunk q of a row = local tile index + 2 * segment
+//   (+ 0 / 1 / 2 for a tile's left-halo, centre and right-halo chunk).  The channel stride
+//   is a multiple of 256 bytes, i.e. every channel group starts on the same bank, on
+//   purpose: a 16-lane group of ds_read_b128 mixes lanes of two channel groups (lanes 0-3
+//   and 12-15 with 20-27, ...), and those are *different tiles* (0-3, 12-15 of one channel,
+//   4-11 of the next), so with equal channel bases their 16-byte chunks fall on disjoint
+//   banks.  A stride that shifted the channel groups against each other would make them
+//   collide.
+//
+// Pipeline (r = step - s_begin): the patch waves read step r+2's raw rows from slot r & 1
+// during step r; the slab waves load step r+4's into registers at the start of step r and
+// write step r+3's (loaded one step earlier) to slot (r+1) & 1 after its MFMAs -- the slot
+// the patch waves finished reading one barrier earlier and read again one barrier later.
+// Rule: a slot is written only in a step in which no wave reads it -- in step r the patch
+// waves read slot r & 1 and nothing else of the ring, the slab waves write slot (r+1) & 1
+// and nothing else, and a barrier separates the steps.  The prologue keeps to it: the
+// patches of steps 0 and 1 come by variant 6's tap loads (both requested before the first
+// barrier, one memory round trip), so no wave reads the ring before step 0; the slab waves
+// fill slot 0 with step 2's rows before that barrier, and slot 1 first in step 0.
+// W % 4 == 0 and W >= 8 only (host).
+//
+// OG = 2 (host variant 17) is the 32-channel workgroup of variant 7 with the ring: 72 + 36
+// KiB, so one workgroup per CU where variant 7 has two.  kDbg (host variants 20-22) are
+// timing ablations with wrong results, like variants 8-10: 8 = one register set for the
+// rows (written in the step that loads them), 1 = the patch waves do not read the ring,
+// 2 / 4 = the slab waves do not load / write the rows.
+template <int kRS>
+struct F4Rows {
+  static constexpr int kCS = (6 * kRS + 15) / 16 * 16;  // chunks per channel
+  static constexpr int kSlot = kC * kCS * 4;            // floats per slot
+};
+
+// Chunk q of a tile-row-major run of 32 tiles starting at t0, whose first segment has n0
+// tiles: segment index in *g, chunk within the segment returned.
+__device__ __forceinline__ int f4_rows_segment(int q, int n0, int TW, int* g) {
+  if (q < n0 + 2) {
+    *g = 0;
+    return q;
+  }
+  const int qq = q - n0 - 2;
+  *g = 1 + qq / (TW + 2);
+  return qq - (*g - 1) * (TW + 2);
+}
+
+template <int kRS, int kPer, int OG = 4, int kDbg = 0>
+__global__ __launch_bounds__(F4Cfg<OG>::kThreads, 1) void f4_conv_rows_kernel(
+    const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ bias,
+    float* __restrict__ y, int R, int H, int W, int O, int Rp, int Op, int TH, int TW, int P,
+    int tblocks, int oblocks, int splits, uint32_t x_bytes) {
+  using Cfg = F4Cfg<OG>;
+  using Rows = F4Rows<kRS>;
+  constexpr int kO = Cfg::kO;
+  constexpr int kBuf = Cfg::kBuf;
+  constexpr int kSlot = Rows::kSlot;
+  // 108 KiB (OG 4) / 72 KiB (OG 2) + 36 KiB (kRS 46) / 50 KiB (kRS 66)
+  __shared__ float lds[2 * kBuf + 2 * kSlot];
+  float* const raw = lds + 2 * kBuf;
+
+  const int nwg = tblocks * oblocks * splits;
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7;
+  const int qq = nwg >> 3, rr = nwg & 7;
+  const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int ob = wgid % oblocks;
+  const int tb = (wgid / oblocks) % tblocks;
+  const int z = wgid / (oblocks * tblocks);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wo = wave % OG;
+  const int wt = wave / OG;
+  const int t0 = tb * kT;
+  const int o0 = ob * kO;
+  const int HW = H * W;
+  const int tpi = TH * TW;
+
+  const int nsteps = Rp / kC;
+  const int s_begin = z * nsteps / splits;
+  const int s_end = (z + 1) * nsteps / splits;
+  const uint32_t step_bytes = static_cast<uint32_t>(kC) * HW * 4;
+  floatx4 acc[kP];
+#pragma unroll
+  for (int i = 0; i < kP; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const __amdgpu_buffer_rsrc_t xr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), static_cast<short>(0),
+                                        static_cast<int>(x_bytes), 0x00020000);
+  // the first segment ends with the tile row of t0
+  const int n0 = min(TW - (t0 % tpi) % TW, kT);
+
+  if (wave < 2) {
+    // -- patch waves: tile t0 + 16*wave + (lane & 15), channel (lane >> 4) of each step --
+    const int tl = wave * 16 + (lane & 15);
+    float* vmine = lds + Cfg::kUImg + ((lane >> 4) * kT + tl) * kP;
+    // the lane's left-halo chunk of row 0 in slot 0; rows and taps are constant offsets
+    const int seg = tl < n0 ? 0 : 1 + (tl - n0) / TW;
+    const float* rmine = raw + ((lane >> 4) * Rows::kCS + tl + 2 * seg) * 4;
+    F4Patch p;
+    f4_fwd_offsets(p, t0 + tl, lane >> 4, P, tpi, TW, R, H, W);
+    // steps 0 and 1 by tap loads: the ring is first read in step 0 (slot 0, step 2's rows)
+    F4Patch first = p;
+    f4_load_patch<false>(first, xr, s_begin * step_bytes);
+    f4_load_patch<false>(p, xr, min(s_begin + 1, s_end - 1) * step_bytes);
+    f4_transform_store(first, vmine);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    auto read_rows = [&](const float* r) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        p.d[i * 6 + 0] = r[i * kRS * 4 + 3];
+        const floatx4 mid = *reinterpret_cast<const floatx4*>(r + i * kRS * 4 + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p.d[i * 6 + 1 + j] = mid[j];
+        p.d[i * 6 + 5] = r[i * kRS * 4 + 8];
+      }
+    };
+    for (int s = s_begin; s < s_end; ++s) {
+      const int buf = (s - s_begin) & 1;
+      f4_transform_store(p, vmine + (buf ^ 1) * kBuf);
+      __builtin_amdgcn_sched_barrier(0);
+      // step s+2's rows (stale past the last step: transformed into a buffer nobody reads)
+      if constexpr ((kDbg & 1) == 0) read_rows(rmine + buf * kSlot);
+      __builtin_amdgcn_sched_barrier(0);
+      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+  } else {
+    // -- slab waves: the step's weight slab by LDS-DMA, and the raw input rows ------------
+    const int stid = tid - 128;
+    const int sw = stid >> 6;
+    constexpr int kGldsWaves = Cfg::kSlabThreads / 64;
+    const int64_t slab_stride = static_cast<int64_t>(Op / 16) * (kC * 16 * kP);
+    const float* ubase = u + static_cast<int64_t>(o0 / 16) * (kC * 16 * kP);
+    // This lane's chunks e = stid + kSlabThreads * k of the [4 c][6 rows][rs chunks] the 32 tiles
+    // touch (rs = 32 + 2 * segments <= kRS): byte offset in x of channel c of the first
+    // step (kBadRow where the chunk is padding) and float index in slot 0.  Lanes past the
+    // last chunk stage one of the first chunks a second time (the same value to the same
+    // place), so the step loop carries no per-lane branch.
+    const int nseg = n0 < kT ? 1 + (kT - n0 + TW - 1) / TW : 1;
+    const int rs = kT + 2 * nseg;
+    uint32_t xoff[kPer];
+    int slot[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const int e = (stid + k * Cfg::kSlabThreads) % (kC * 6 * rs);
+      const int c = e / (6 * rs);
+      const int er = e - c * 6 * rs;
+      const int i = er / rs;
+      const int q = er - i * rs;
+      int g;
+      const int ck = f4_rows_segment(q, n0, TW, &g);
+      const int tf = g == 0 ? t0 : t0 + n0 + (g - 1) * TW;  // the segment's first tile
+      const int n = tf / tpi;
+      const int rem = tf - n * tpi;
+      const int ty = rem / TW;
+      const int yy = 4 * ty - 1 + i;
+      const int xx = 4 * (rem - ty * TW - 1 + ck);
+      const bool ok = tf < P && yy >= 0 && yy < H && xx >= 0 && xx < W;
+      const int64_t idx = (static_cast<int64_t>(n) * R + c) * HW + static_cast<int64_t>(yy) * W + xx;
+      xoff[k] = ok ? static_cast<uint32_t>(idx * 4) : kBadRow;
+      slot[k] = (c * Rows::kCS + i * kRS + q) * 4;
+    }
+    static_assert(kPer * Cfg::kSlabThreads >= kC * 6 * kRS, "every chunk has a lane");
+    // The channel advance goes into the range-checked offset (see f4_load_patch).
+    auto load_rows = [&](floatx4 (&rreg)[kPer], int s) {
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(xr, xoff[k] + s * step_bytes, 0, 0);
+        rreg[k] = floatx4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                          __uint_as_float(v[3])};
+      }
+    };
+    // The LDS writes are spelled out: before a plain LDS store the compiler retires every
+    // outstanding LDS-DMA (it cannot tell the slab image from the ring), which here means
+    // vmcnt(0) and the rows just requested.  It still waits for the stored registers.
+    const uint32_t raw_lds = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_void_t*)raw));
+    auto store_rows = [&](const floatx4 (&rreg)[kPer], int slot_index) {
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        const uint32_t a = raw_lds + (slot_index * kSlot + slot[k]) * 4;
+        asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(rreg[k]) : "memory");
+      }
+    };
+    // kDeep: the rows loaded during one step stay in flight across its barrier (an HBM
+    // round trip is longer than a step) and are written to LDS during the next; the weight
+    // slab's DMA is issued before them, so vmcnt(kPer) retires it and leaves them out.
+    // Otherwise (5 chunks per lane: planes narrower than 24, which stay in L2) one register
+    // set: loaded at the start of a step, written at its end.
+    // Every staged buffer is read one phase after the wait that retires it: slab and rows
+    // are retired (vmcnt / lgkmcnt) before the barrier that ends a step and read after it.
+    constexpr bool kDeep = kPer <= 3 && (kDbg & 8) == 0;
+    floatx4 rreg[kPer];
+    // step s_begin + 2's rows into slot 0 (past the last step: its rows again, which nobody
+    // reads); slot 1 is first written in step 0
+    load_rows(rreg, min(s_begin + 2, s_end - 1));
+    f4_glds_slab<Cfg, kGldsWaves>(ubase + s_begin * slab_stride, lds, sw, lane);
+    store_rows(rreg, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (kDeep) {
+      load_rows(rreg, min(s_begin + 3, s_end - 1));
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPer) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // One step; slot (buf ^ 1) gets step s+3's rows.  kDeep: they are in `cur`, loaded
+    // during step s-1, and step s+4's take off into `nxt` (two steps per loop trip, so the
+    // two register sets swap roles without a copy, which would wait for the loads).
+    auto step = [&](int s, int buf, floatx4 (&cur)[kPer], floatx4 (&nxt)[kPer]) {
+      if constexpr (!kDeep && (kDbg & 2) == 0) load_rows(cur, min(s + 3, s_end - 1));
+      if (s + 1 < s_end)
+        f4_glds_slab<Cfg, kGldsWaves>(ubase + (s + 1) * slab_stride, lds + (buf ^ 1) * kBuf, sw,
+                                      lane);
+      if constexpr (kDeep && (kDbg & 2) == 0) load_rows(nxt, min(s + 4, s_end - 1));
+      __builtin_amdgcn_sched_barrier(0);
+      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr ((kDbg & 4) == 0) store_rows(cur, buf ^ 1);
+      if constexpr (kDeep) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPer) : "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    };
+    floatx4 rodd[kPer];
+    int s = s_begin;
+    for (; s + 1 < s_end; s += 2) {
+      step(s, 0, rreg, rodd);
+      step(s + 1, 1, rodd, rreg);
+    }
+    if (s < s_end) step(s, 0, rreg, rodd);
+  }
+
+  const int tp = t0 + wt * 16 + (lane & 15);
+  if (tp >= P) return;
+  float* ydst = y + static_cast<int64_t>(z) * (P / tpi) * O * HW;
+  f4_output_transform(acc, ydst, bias != nullptr && splits == 1 ? bias : nullptr, tp, tpi, TW,
+                      H, W, O, o0 + wo * 16 + 4 * (lane >> 4));
+}
+
 // ---- non-fused variant: input transform pass + two-operand LDS-DMA GEMM ----------------
 // Variants 14 / 15 take the input transform out of the GEMM kernel (cuDNN's
 // WINOGRAD_NONFUSED split): f4_input_transform_kernel writes V = B^T d B of every (tile,
@@ -1234,6 +1494,195 @@ __global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_kernel(
   }
 
   // -- dW = G^T dU G; lane holds c = c0 + wt*16 + (lane & 15), k = k0 + wo*16 + 4(lane>>4) + r
+  f4_wgrad_epilogue(acc, dw + static_cast<int64_t>(z) * K * C * 9, c0 + wt * 16 + (lane & 15),
+                    k0 + wo * 16 + 4 * (lane >> 4), C, K, accum);
+}
+
+// wino4_wgrad variant 3: f4_wgrad_kernel with the x operand's raw input rows staged through
+// LDS, as f4_conv_rows_kernel does (W % 4 == 0 and at least 4 tiles per row: host).  A step
+// is 4 consecutive tiles x 32 channels: one row segment of 6 chunks, or, where the tiles
+// wrap to the next tile row or image, two segments of 8 chunks in all.  Waves 4-5, which
+// only multiply in f4_wgrad_kernel, fetch the step's [32 c][6 rows][8 chunks] as aligned
+// 16-byte buffer loads (12 per lane; 8 lanes cover a row's 128 bytes) into a two-slot ring
+// behind the two [M' | V] buffers; the patch waves (lane = channel, lane >> 4 = tile) read
+// their taps from it.  The channel stride is 49 chunks (16 bytes past a multiple of 256):
+// the lanes of a ds_read_b128 group are 16 different channels of (mostly) one chunk
+// column, which the odd stride spreads over the banks.
+// Ring rule as in f4_conv_rows_kernel: in step r the patch waves read slot r & 1 only (step
+// r+2's rows), the staging waves write slot (r+1) & 1 only (step r+3's), barriers between
+// steps; the patches of steps 0 and 1 come by tap loads, slot 0 is filled before the first
+// barrier.  The staging waves hold no LDS-DMA, so __syncthreads orders everything.
+constexpr int kWgRS = 8;                       // chunks per staged row
+constexpr int kWgCS = 6 * kWgRS + 1;           // chunks per channel
+constexpr int kWgSlot = 32 * kWgCS * 4;        // floats per slot (24.5 KiB)
+
+__device__ __forceinline__ F4TileCursor f4_cursor_at(int t, int TH, int TW) {
+  F4TileCursor cur;
+  const int tpi = TH * TW;
+  cur.n = t / tpi;
+  const int rem = t - cur.n * tpi;
+  cur.ty = rem / TW;
+  cur.tx = rem - cur.ty * TW;
+  return cur;
+}
+
+__global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_rows_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dw, int N,
+    int C, int K, int H, int W, int TH, int TW, int P, int cblocks, int kblocks, int splits,
+    uint32_t x_bytes, uint32_t dy_bytes, bool accum) {
+  using Cfg = F4Cfg<4>;
+  constexpr int kBuf = Cfg::kBuf;
+  __shared__ float lds[2 * kBuf + 2 * kWgSlot];  // 108 + 49 KiB
+  float* const raw = lds + 2 * kBuf;
+
+  const int nwg = cblocks * kblocks * splits;
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7;
+  const int qq = nwg >> 3, rr = nwg & 7;
+  const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int cb = wgid % cblocks;
+  const int kb = (wgid / cblocks) % kblocks;
+  const int z = wgid / (cblocks * kblocks);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wo = wave & 3;   // 16 k rows
+  const int wt = wave >> 2;  // 16 c columns
+  const int c0 = cb * 32;
+  const int k0 = kb * 64;
+
+  const int nsteps = (P + 3) / 4;
+  const int s_begin = static_cast<int>(static_cast<int64_t>(z) * nsteps / splits);
+  const int s_end = static_cast<int>(static_cast<int64_t>(z + 1) * nsteps / splits);
+  floatx4 acc[kP];
+#pragma unroll
+  for (int i = 0; i < kP; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const __amdgpu_buffer_rsrc_t xr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), static_cast<short>(0),
+                                        static_cast<int>(x_bytes), 0x00020000);
+  const bool dy_wave = (wave & 2) != 0;  // waves 2, 3, 6, 7
+
+  if (wave < 2) {
+    // -- input patches: channel c0 + 16*wave + (lane & 15), tile (lane >> 4) of the step --
+    const int j = lane >> 4;
+    const int cc = 16 * wave + (lane & 15);
+    float* vmine = lds + Cfg::kUImg + (j * kT + cc) * kP;
+    const float* rmine = raw + (cc * kWgCS + j) * 4;
+    F4TileCursor cur = f4_cursor_at(4 * s_begin + j, TH, TW);
+    F4Patch p, first;
+    f4_patch_offsets(first, cur, c0 + cc, N, C, H, W);
+    f4_load_patch<true>(first, xr, 0);
+    f4_cursor_advance(cur, TH, TW);
+    f4_patch_offsets(p, cur, c0 + cc, N, C, H, W);
+    f4_load_patch<true>(p, xr, 0);
+    f4_transform_store(first, vmine);
+    __syncthreads();
+    // first tile of the step whose rows are read next (s + 2)
+    F4TileCursor rc = f4_cursor_at(4 * (s_begin + 2), TH, TW);
+    for (int s = s_begin; s < s_end; ++s) {
+      const int buf = (s - s_begin) & 1;
+      f4_transform_store(p, vmine + (buf ^ 1) * kBuf);
+      __builtin_amdgcn_sched_barrier(0);
+      // step s+2's rows (past the split's end: staged, never read); a tile behind the row
+      // break sits two chunks further on
+      const float* r = rmine + buf * kWgSlot + (j >= TW - rc.tx ? 8 : 0);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        p.d[i * 6 + 0] = r[i * kWgRS * 4 + 3];
+        const floatx4 mid = *reinterpret_cast<const floatx4*>(r + i * kWgRS * 4 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) p.d[i * 6 + 1 + e] = mid[e];
+        p.d[i * 6 + 5] = r[i * kWgRS * 4 + 8];
+      }
+      f4_cursor_advance(rc, TH, TW);
+      __builtin_amdgcn_sched_barrier(0);
+      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      __syncthreads();
+    }
+  } else if (dy_wave) {
+    // -- gradient tiles: channel k0 + 16*d + (lane & 15), tile (lane >> 4) of the step --
+    const __amdgpu_buffer_rsrc_t dyr =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy), static_cast<short>(0),
+                                          static_cast<int>(dy_bytes), 0x00020000);
+    F4TileCursor cur = f4_cursor_at(4 * s_begin + (lane >> 4), TH, TW);
+    const int d = (wave & 1) | ((wave >> 2) << 1);
+    const int k = k0 + 16 * d + (lane & 15);
+    float* mmine = lds + ((d * kC + (lane >> 4)) * 16 + (lane & 15)) * kP;
+    float g[16];
+    f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
+    f4_dy_transform_store(g, mmine);
+    __syncthreads();
+    f4_cursor_advance(cur, TH, TW);
+    f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
+    for (int s = s_begin; s < s_end; ++s) {
+      const int buf = (s - s_begin) & 1;
+      f4_dy_transform_store(g, mmine + (buf ^ 1) * kBuf);
+      __builtin_amdgcn_sched_barrier(0);
+      f4_cursor_advance(cur, TH, TW);
+      f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
+      __builtin_amdgcn_sched_barrier(0);
+      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      __syncthreads();
+    }
+  } else {
+    // -- staging waves: lane = (chunk q of a row, channel cl of 16); 12 chunks per lane:
+    //    row k % 6 of channel c0 + 16 * (k / 6) + cl
+    const int sl = tid - 256;
+    const int q = sl & 7;
+    const int cl = sl >> 3;
+    const int HW = H * W;
+    floatx4 rreg[12];
+    auto load_rows = [&](const F4TileCursor& c4) {
+      // chunk q of the step whose first tile is c4: first segment n0 tiles, then the rest
+      const int n0 = min(TW - c4.tx, 4);
+      int n = c4.n, ty = c4.ty, xc = c4.tx - 1 + q;
+      bool used = q < n0 + 2;
+      if (!used && n0 < 4) {
+        used = true;  // n0 + 2 + (4 - n0) + 2 = 8 chunks
+        xc = q - n0 - 3;
+        if (++ty == TH) {
+          ty = 0;
+          ++n;
+        }
+      }
+      const int xx = 4 * xc;
+      const bool okx = used && n < N && xx >= 0 && xx < W;
+      const int y0 = 4 * ty - 1;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        const int row = k % 6;
+        const int c = c0 + 16 * (k / 6) + cl;
+        const bool ok = okx && c < C && y0 + row >= 0 && y0 + row < H;
+        const uint32_t idx = (static_cast<uint32_t>(n) * C + c) * HW + (y0 + row) * W + xx;
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(xr, ok ? idx * 4 : kBadRow, 0, 0);
+        rreg[k] = floatx4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                          __uint_as_float(v[3])};
+      }
+    };
+    auto store_rows = [&](float* dst) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k)
+        *reinterpret_cast<floatx4*>(dst + ((16 * (k / 6) + cl) * kWgCS + (k % 6) * kWgRS + q) * 4) =
+            rreg[k];
+    };
+    F4TileCursor sc = f4_cursor_at(4 * (s_begin + 2), TH, TW);
+    load_rows(sc);
+    store_rows(raw);
+    __syncthreads();
+    for (int s = s_begin; s < s_end; ++s) {
+      const int buf = (s - s_begin) & 1;
+      f4_cursor_advance(sc, TH, TW);  // step s + 3
+      load_rows(sc);
+      __builtin_amdgcn_sched_barrier(0);
+      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      __builtin_amdgcn_sched_barrier(0);
+      store_rows(raw + (buf ^ 1) * kWgSlot);
+      __syncthreads();
+    }
+  }
+
   f4_wgrad_epilogue(acc, dw + static_cast<int64_t>(z) * K * C * 9, c0 + wt * 16 + (lane & 15),
                     k0 + wo * 16 + 4 * (lane >> 4), C, K, accum);
 }
@@ -2342,8 +2791,15 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
                     int variant, int splits) {
   WinoPlan plan;
   plan.variant = (variant >= 4 && variant <= 12 && variant != 11) || variant == 14 ||
-                         variant == 15 || variant == 18 ? variant : 5;
-  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ? 2 : 4;
+                         variant == 15 || variant == 16 || variant == 17 || variant == 18 ||
+                         (variant >= 20 && variant <= 22) ? variant : 5;
+  // the row-staged kernel takes whole 16-byte chunks and at most 17 row segments
+  if (plan.variant == 16 && ((w & 3) != 0 || w < 8)) plan.variant = 6;
+  // the 32-channel ring and the ablations: the 7-segment instance only
+  if (plan.variant == 17 && ((w & 3) != 0 || w < 24)) plan.variant = 7;
+  if (plan.variant >= 20 && plan.variant <= 22 && ((w & 3) != 0 || w < 24)) plan.variant = 6;
+  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ||
+                         plan.variant == 17 ? 2 : 4;
   const int64_t P = n * ((h + 3) / 4) * ((w + 3) / 4);
   const int64_t blocks = ((P + kT - 1) / kT) * ((out_channels + 16 * og - 1) / (16 * og));
   const int64_t steps = wino4_pad_reduction(red_channels) / kC;
@@ -2372,7 +2828,7 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
     plan.splits = static_cast<int>(best);
   }
   plan.workspace = plan.splits > 1 ? plan.splits * n * out_channels * h * w : 0;
-  if (plan.variant >= 14) {  // + the transformed input V4[P/32][Rp/4][4][32][36], first
+  if (plan.variant == 14 || plan.variant == 15) {  // + the transformed input V4[P/32][Rp/4][4][32][36], first
     plan.workspace += ((P + kT - 1) / kT) * kT * wino4_pad_reduction(red_channels) * kP;
   }
   return plan;
@@ -2385,7 +2841,8 @@ void launch_wino4_conv(const float* x, const float* u, const float* bias, float*
   const int64_t Op = wino4_pad_output(out_channels);
   const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
   const int64_t P = n * th * tw;
-  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ? 2 : 4;
+  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ||
+                         plan.variant == 17 ? 2 : 4;
   const int tblocks = static_cast<int>((P + kT - 1) / kT);
   if (plan.variant == 18) {
     const int oblocks4 = static_cast<int>((out_channels + 63) / 64);
@@ -2406,7 +2863,7 @@ void launch_wino4_conv(const float* x, const float* u, const float* bias, float*
   const int oblocks = static_cast<int>((out_channels + 16 * og - 1) / (16 * og));
   const int splits = plan.splits;
   const int64_t nwg = static_cast<int64_t>(tblocks) * oblocks * splits;
-  if (plan.variant >= 14) {
+  if (plan.variant == 14 || plan.variant == 15) {
     float* vbuf = ws;
     const int64_t vtotal = static_cast<int64_t>(tblocks) * kT * Rp;  // threads
     float* split_ws = ws + vtotal * kP;
@@ -2437,6 +2894,12 @@ void launch_wino4_conv(const float* x, const float* u, const float* bias, float*
   if (plan.variant == 10) kernel = f4_conv_kernel<4, false, true, 3>;
   if (plan.variant == 12) kernel = vec ? f4_conv_kernel<4, true, true> : f4_conv_kernel<4, false, true>;
   if (plan.variant == 7) kernel = vec ? f4_conv_kernel<2, true, true> : f4_conv_kernel<2, false, true>;
+  // <= 7 row segments per workgroup from 6 tiles per row on, <= 17 from 2
+  if (plan.variant == 16) kernel = tw >= 6 ? f4_conv_rows_kernel<46, 3> : f4_conv_rows_kernel<66, 5>;
+  if (plan.variant == 17) kernel = f4_conv_rows_kernel<46, 9, 2>;
+  if (plan.variant == 20) kernel = f4_conv_rows_kernel<46, 3, 4, 8>;
+  if (plan.variant == 21) kernel = f4_conv_rows_kernel<46, 3, 4, 1>;
+  if (plan.variant == 22) kernel = f4_conv_rows_kernel<46, 3, 4, 7>;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(128 * og), 0, stream,
                      x, u, bias, splits > 1 ? ws : y, static_cast<int>(red_channels),
                      static_cast<int>(h), static_cast<int>(w), static_cast<int>(out_channels),
@@ -2528,6 +2991,8 @@ void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, i
                        accum && splits == 1);
   } else {
     auto kernel = (w & 3) == 0 ? f4_wgrad_kernel<true> : f4_wgrad_kernel<false>;
+    // variant 3 (row-staged x operand): whole 16-byte chunks, at most one row break per step
+    if (variant == 3 && (w & 3) == 0 && w >= 16) kernel = f4_wgrad_rows_kernel;
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
                        stream, x, dy, splits > 1 ? partial : dw, static_cast<int>(n),
                        static_cast<int>(c), static_cast<int>(k), static_cast<int>(h),

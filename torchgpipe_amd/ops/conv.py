@@ -340,9 +340,13 @@ def clear_winograd_caches(module: torch.nn.Module) -> None:
 # 1.17-1.45x faster than F(2x2) from 12^2 up, slower at 6^2 (a 4x4 tile wastes 5/9 of a
 # 6-pixel plane).  The F(4x4) kernel's 32-bit offsets need the input below 1 GiB.
 F4_MIN_PLANE = 8
-# Fused F(4x4) forward / backward-data kernel for < 512 channels: 6 (slab one step ahead)
-# or 18 (slab ring, two steps ahead; csrc/winograd_f4.hip).  TGPIPE_F4_FUSED_VARIANT.
-_F4_FUSED_VARIANT = int(os.environ.get('TGPIPE_F4_FUSED_VARIANT', '6'))
+# Fused F(4x4) forward / backward-data kernel for < 512 channels: 16 (6 with the raw input
+# rows staged through LDS; runs as 6 where W % 4 != 0), 6 (slab one step ahead, per-tap
+# patch loads) or 18 (slab ring, two steps ahead; csrc/winograd_f4.hip).  16 is faster than
+# 6 on every U-Net shape from 24^2 up and no faster below (profiles/r9/f4_rows), so
+# narrower planes stay on 6.  TGPIPE_F4_FUSED_VARIANT.
+_F4_FUSED_VARIANT = int(os.environ.get('TGPIPE_F4_FUSED_VARIANT', '16'))
+F4_ROWS_MIN_WIDTH = 24
 F4_MAX_BYTES = (1 << 30) - 64
 
 
@@ -428,6 +432,8 @@ def _conv(x: Tensor, cache: _TransformCache, weight: Tensor, bias: Optional[Tens
             variant = 15 if small else 14
         else:
             variant = 7 if out_channels <= 32 or blocks < 160 else _F4_FUSED_VARIANT
+            if variant == 16 and x.shape[3] < F4_ROWS_MIN_WIDTH:
+                variant = 6
         return ops.wino4_conv(x, cache.get(weight, flip, True), bias, out_channels, variant)
     return ops.wino_conv(x, cache.get(weight, flip), bias, out_channels)
 
@@ -578,7 +584,9 @@ def _wgrad_f4_variant(x: Tensor, weight: Tensor) -> int:
     time against 130.5 ms for the non-fused passes (profiles/r6/bg_input_cpt/
     p4_new_wgrad_rule.md), so the rule stayed as it was."""
     if min(weight.shape[0], weight.shape[1]) < 512:
-        return 0
+        # fused kernel; with the x operand's rows staged through LDS (variant 3) where that
+        # measured faster: planes from 24 wide, W % 4 == 0 (1.5-4 %, profiles/r9/f4_rows)
+        return 3 if x.shape[3] % 4 == 0 and x.shape[3] >= F4_ROWS_MIN_WIDTH else 0
     tiles = x.shape[0] * -(-x.shape[2] // 4) * -(-x.shape[3] // 4)
     return 2 if WGRAD_EMU and tiles >= WGRAD_EMU_MIN_TILES else 1
 
