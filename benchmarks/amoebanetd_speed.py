@@ -7,7 +7,7 @@ Checkpointing is 'always' for m=1 and 'except_last' otherwise.
 import torch
 import torch.nn.functional as F
 
-from common import parser, run_speed
+from common import add_conv_precision, parser, run_speed, set_conv_precision
 
 from torchgpipe_amd.models import amoebanetd
 
@@ -18,6 +18,7 @@ def exp(batch, chunks, balance):
 
 
 EXPERIMENTS = {
+    'n1m32': exp(640, 32, [24]),  # (not in the reference: bench.py's one-GPU AmoebaNet section)
     'n2m1': exp(96, 1, [7, 17]),
     'n2m4': exp(256, 4, [9, 15]),
     'n2m32': exp(1280, 32, [9, 15]),
@@ -31,7 +32,10 @@ EXPERIMENTS = {
 
 
 def main() -> None:
-    args = parser(__doc__, EXPERIMENTS).parse_args()
+    p = parser(__doc__, EXPERIMENTS)
+    add_conv_precision(p)
+    args = p.parse_args()
+    set_conv_precision(args)
     run_speed(args, EXPERIMENTS[args.experiment],
               lambda: amoebanetd(num_classes=1000, num_layers=18, num_filters=256),
               (3, 224, 224), lambda b, d: torch.randint(1000, (b,), device=d),

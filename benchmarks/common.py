@@ -50,6 +50,19 @@ def parser(description: str, experiments: Dict[str, Experiment]) -> argparse.Arg
     return p
 
 
+def add_conv_precision(p: argparse.ArgumentParser) -> None:
+    """``--conv-precision``: apply it with :func:`set_conv_precision` before the model is built."""
+    from torchgpipe_amd.ops import precision
+    p.add_argument('--conv-precision', choices=precision.LEVELS, default='highest',
+                   help='fp32 precision of the split-bf16 convolution kernels '
+                        '(torchgpipe_amd/ops/precision.py)')
+
+
+def set_conv_precision(args: argparse.Namespace) -> None:
+    from torchgpipe_amd.ops import precision
+    precision.set_conv_precision(args.conv_precision)
+
+
 def parse_devices(value: Optional[str]) -> List[int]:
     if value is None:
         return list(range(torch.cuda.device_count()))
@@ -150,7 +163,9 @@ def run_speed(args: argparse.Namespace, experiment: Experiment,
         if args.json:
             print(json.dumps({'experiment': args.experiment, 'samples_per_sec': mean,
                               'batch': batch, 'chunks': chunks, 'balance': balance,
-                              'mode': args.mode}), flush=True)
+                              'mode': args.mode,
+                              'conv_precision': getattr(args, 'conv_precision', 'highest')}),
+                  flush=True)
     if world > 1:
         dist.destroy_process_group()
     return mean

@@ -59,9 +59,13 @@ def main() -> None:
     p = argparse.ArgumentParser(description=__doc__)
     p.add_argument('--micro-batch', type=int, default=20)
     p.add_argument('--out', default='')
+    p.add_argument('--conv-precision', choices=['highest', 'high', 'medium'], default='highest',
+                   help='fp32 precision of the split-bf16 kernels (the MIOpen columns are '
+                        'exact fp32 at every level)')
     args = p.parse_args()
-    from torchgpipe_amd.ops import _ext
+    from torchgpipe_amd.ops import _ext, precision
     ops = _ext.require()
+    precision.set_conv_precision(args.conv_precision)
     rows = []
     tot = {'ours': 0.0, 'miopen': 0.0}
     for (xs, ws, stride, pad), count in capture(args.micro_batch).items():
@@ -76,7 +80,7 @@ def main() -> None:
         w_t = w.transpose(0, 1).contiguous()
         flops = 2.0 * y.numel() * ws[1] * kh * kw
         r = {'x': xs, 'w': ws, 'stride': stride, 'pad': pad, 'count': count,
-             'gflop': round(flops / 1e9, 3)}
+             'gflop': round(flops / 1e9, 3), 'conv_precision': args.conv_precision}
         for name, fn in [
             ('fwd', lambda: ops.conv_gemm_forward(x, w, geo, True)),
             ('bwd_data', lambda: ops.conv_gemm_backward_data(dz, x, w, geo, True, w_t)),
@@ -102,7 +106,8 @@ def main() -> None:
                       'weighted_total_us_miopen': round(tot['miopen'], 1)}), flush=True)
     if args.out:
         with open(args.out, 'w') as f:
-            json.dump({'micro_batch': args.micro_batch, 'rows': rows, 'totals': tot}, f, indent=1)
+            json.dump({'micro_batch': args.micro_batch, 'conv_precision': args.conv_precision,
+                       'rows': rows, 'totals': tot}, f, indent=1)
 
 
 if __name__ == '__main__':

@@ -37,9 +37,13 @@ def main() -> None:
     p.add_argument('--micro-batch', type=int, default=20, help='images per shape')
     p.add_argument('--out', default='')
     p.add_argument('--set', choices=['amoebanet', 'resnet'], default='amoebanet')
+    p.add_argument('--conv-precision', choices=['highest', 'high', 'medium'], default='highest',
+                   help='fp32 precision of the split-bf16 configurations (the f32 ones, 0-6, '
+                        'are exact at every level)')
     a = p.parse_args()
-    from torchgpipe_amd.ops import _ext
+    from torchgpipe_amd.ops import _ext, precision
     ops = _ext.require()
+    precision.set_conv_precision(a.conv_precision)
     out = []
     for _, ci, h, co, kh, kw in (SHAPES if a.set == 'amoebanet' else RESNET_SHAPES):
         n = a.micro_batch
@@ -52,6 +56,7 @@ def main() -> None:
             cands = sorted(([CFG[int(r[i])], int(r[i + 1]), round(r[i + 2], 2)]
                             for i in range(0, len(r), 3)), key=lambda c: c[2])
             row = {'shape': [n, ci, h, co, kh, kw], 'mode': name, 'gflop': round(gflop, 3),
+                   'conv_precision': a.conv_precision,
                    'best_us': cands[0][2], 'best_tflops': round(gflop / cands[0][2] * 1e3, 1),
                    'top': cands[:6]}
             # the double- vs single-buffered 8-wave split-bf16 tile, each at its best split

@@ -61,12 +61,18 @@ def main() -> None:
     p.add_argument('--rounds', type=int, default=5, help='timed windows')
     p.add_argument('--models', default=','.join(MODELS), help='comma-separated subset')
     p.add_argument('--label', default='', help='free text copied into the result')
+    p.add_argument('--conv-precision', choices=['highest', 'high', 'medium'], default='highest',
+                   help='fp32 precision of the split-bf16 convolution kernels '
+                        '(torchgpipe_amd/ops/precision.py)')
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('eval_speed needs a GPU: a CPU run would time nothing of interest')
     result = {'benchmark': 'eval_speed', 'label': args.label, 'batch': args.batch,
               'iters': args.iters, 'rounds': args.rounds,
-              'device': torch.cuda.get_device_name(0)}
+              'device': torch.cuda.get_device_name(0), 'conv_precision': args.conv_precision}
+    if args.conv_precision != 'highest':
+        from torchgpipe_amd.ops import precision
+        precision.set_conv_precision(args.conv_precision)
     for name in args.models.split(','):
         result[name] = measure(name, args.batch, args.warmup, args.iters, args.rounds)
     print(json.dumps(result), flush=True)

@@ -5,7 +5,7 @@
 import torch
 import torch.nn.functional as F
 
-from common import parser, run_speed
+from common import add_conv_precision, parser, run_speed, set_conv_precision
 
 from torchgpipe_amd.models.resnet import build_resnet
 
@@ -25,7 +25,9 @@ def main() -> None:
     p.add_argument('--plain', action='store_true',
                    help='plain nn layers (MIOpen convolutions / BatchNorm) instead of the fused '
                         'Conv-BN-ReLU runs (ops/fusion.py)')
+    add_conv_precision(p)
     args = p.parse_args()
+    set_conv_precision(args)
     run_speed(args, EXPERIMENTS[args.experiment],
               lambda: build_resnet([3, 4, 23, 3], num_classes=1000, fused=not args.plain),
               (3, 224, 224), lambda b, d: torch.randint(1000, (b,), device=d),

@@ -46,6 +46,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <stdexcept>
 #include <type_traits>
@@ -297,15 +298,31 @@ __device__ __forceinline__ int emu_off(int j, int row) {  // in bf16 elements
   return (j * ROWS + (row ^ (2 * j))) * 8;
 }
 
-template <int ROWS>
+// Precision levels (conv_precision, kernels.h): LV 0 `highest` keeps all six products, LV 1
+// `high` the three without a lo part (hi.hi, hi.mid, mid.hi: 3 * 2^-18 |a b| left out at
+// worst), LV 2 `medium` hi.hi alone (2^-8).  A level works on its first 3 - LV planes only:
+// the others are neither split off, stored, copied from a pre-split image nor read.
+template <int ROWS, int LV = 0>
 __device__ __forceinline__ void store_emu_quad(float* img, const floatx4& v, int row, int q) {
-  bf16x4 hi, mid, lo;
-  split3(v, hi, mid, lo);
-  __bf16* p = reinterpret_cast<__bf16*>(img) + emu_off<ROWS>(q >> 1, row) + 4 * (q & 1);
   constexpr int kPlane = kBK * ROWS;
-  *reinterpret_cast<bf16x4*>(p) = hi;
-  *reinterpret_cast<bf16x4*>(p + kPlane) = mid;
-  *reinterpret_cast<bf16x4*>(p + 2 * kPlane) = lo;
+  if constexpr (LV == 0) {
+    bf16x4 hi, mid, lo;
+    split3(v, hi, mid, lo);
+    __bf16* p = reinterpret_cast<__bf16*>(img) + emu_off<ROWS>(q >> 1, row) + 4 * (q & 1);
+    *reinterpret_cast<bf16x4*>(p) = hi;
+    *reinterpret_cast<bf16x4*>(p + kPlane) = mid;
+    *reinterpret_cast<bf16x4*>(p + 2 * kPlane) = lo;
+  } else {
+    bf16x4 hi, mid;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      hi[e] = static_cast<__bf16>(v[e]);
+      if constexpr (LV == 1) mid[e] = static_cast<__bf16>(v[e] - static_cast<float>(hi[e]));
+    }
+    __bf16* p = reinterpret_cast<__bf16*>(img) + emu_off<ROWS>(q >> 1, row) + 4 * (q & 1);
+    *reinterpret_cast<bf16x4*>(p) = hi;
+    if constexpr (LV == 1) *reinterpret_cast<bf16x4*>(p + kPlane) = mid;
+  }
 }
 
 // ---- the GEMM core ------------------------------------------------------------------------
@@ -313,7 +330,11 @@ __device__ __forceinline__ void store_emu_quad(float* img, const floatx4& v, int
 // EMU stage: two k steps of 16; per 32 x 32 tile and step six MFMAs (small parts first).
 // All fragments of the stage are read ahead of its MFMAs; `between(0..3)` carries the next
 // stage's loads (after the first four MFMA groups: the stage is 3/8 as long as an f32 one).
-template <int CFG, typename Between>
+// LV 1 / 2 run the last three / the last one of the six on two / one plane(s).  Their stages
+// are 6 / 2 MFMA groups long, so the four load hooks move: LV 1 behind its first four groups
+// (the three of step 0 and the first of step 1: two groups still cover the loads), LV 2 two
+// behind each of its two groups (the second pair issues while the last MFMAs execute).
+template <int CFG, int LV, typename Between>
 __device__ __forceinline__ void mfma_stage_emu(floatx16 (&acc)[Cfg<CFG>::TM][Cfg<CFG>::TN],
                                                const float* aimg, const float* bimg, int lane,
                                                int wm, int wn, Between&& between) {
@@ -323,14 +344,28 @@ __device__ __forceinline__ void mfma_stage_emu(floatx16 (&acc)[Cfg<CFG>::TM][Cfg
   const __bf16* ab = reinterpret_cast<const __bf16*>(aimg);
   const __bf16* bb = reinterpret_cast<const __bf16*>(bimg);
   constexpr int kPairs[6][2] = {{2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
+  constexpr int P = 3 - LV;                         // planes read
+  constexpr int T0 = LV == 0 ? 0 : (LV == 1 ? 3 : 5);  // first product kept
+  static_assert(LV >= 0 && LV <= 2 && S == 2, "hook placement assumes two k steps");
+  auto hook = [&](int s, int t) {  // after MFMA group t of step s
+    if constexpr (LV == 0) {
+      if (s == 0 && t < 4) between(t);
+    } else if constexpr (LV == 1) {
+      const int grp = 3 * s + t - T0;
+      if (grp < 4) between(grp);
+    } else {
+      between(2 * s);
+      between(2 * s + 1);
+    }
+  };
   if constexpr (C::SINGLE) {
     // per 16-deep step: its fragments, then its MFMAs (the other workgroup's waves cover
     // the read latency; a whole stage of fragments would not fit 128 registers)
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      bf16x8 a[3][WM], b[3][WN];
+      bf16x8 a[P][WM], b[P][WN];
 #pragma unroll
-      for (int p = 0; p < 3; ++p) {
+      for (int p = 0; p < P; ++p) {
 #pragma unroll
         for (int i = 0; i < WM; ++i)
           a[p][i] = *reinterpret_cast<const bf16x8*>(
@@ -341,23 +376,23 @@ __device__ __forceinline__ void mfma_stage_emu(floatx16 (&acc)[Cfg<CFG>::TM][Cfg
               bb + p * kBK * C::BN + emu_off<C::BN>(2 * s + h, wn * 32 * WN + j * 32 + l32));
       }
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
+      for (int t = T0; t < 6; ++t) {
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
           for (int j = 0; j < WN; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                 a[kPairs[t][0]][i], b[kPairs[t][1]][j], acc[i][j], 0, 0, 0);
-        if (s == 0 && t < 4) between(t);
+        hook(s, t);
       }
     }
     return;
   }
-  bf16x8 a[S][3][WM], b[S][3][WN];
+  bf16x8 a[S][P][WM], b[S][P][WN];
 #pragma unroll
   for (int s = 0; s < S; ++s)
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < P; ++p) {
 #pragma unroll
       for (int i = 0; i < WM; ++i)
         a[s][p][i] = *reinterpret_cast<const bf16x8*>(
@@ -371,14 +406,14 @@ __device__ __forceinline__ void mfma_stage_emu(floatx16 (&acc)[Cfg<CFG>::TM][Cfg
 #pragma unroll
   for (int s = 0; s < S; ++s) {
 #pragma unroll
-    for (int t = 0; t < 6; ++t) {
+    for (int t = T0; t < 6; ++t) {
 #pragma unroll
       for (int i = 0; i < WM; ++i)
 #pragma unroll
         for (int j = 0; j < WN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               a[s][kPairs[t][0]][i], b[s][kPairs[t][1]][j], acc[i][j], 0, 0, 0);
-      if (s == 0 && t < 4) between(t);  // the loads within the stage's first third
+      hook(s, t);  // (LV 0: the loads within the stage's first third)
     }
   }
 }
@@ -511,7 +546,8 @@ __device__ __forceinline__ Col make_col(const Geo& g, int j, int N) {
 // bf16, conv_gemm_presplit_kernel) -- the weights, split once per step instead of by every
 // column block of every micro-batch; each thread stages whole k octets of it (three 16-byte
 // loads and three ds_write_b128 per octet, no split arithmetic).
-template <int MODE, int CFG, bool kPlain, bool kPreA>
+// LV (EMU configurations): the precision level of the products, see store_emu_quad.
+template <int MODE, int CFG, bool kPlain, bool kPreA, int LV = 0>
 __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void conv_gemm_kernel(
     const float* __restrict__ a_src, const float* __restrict__ b_src,
     const float* __restrict__ x_mask, float* __restrict__ out, float* __restrict__ part_mean,
@@ -582,7 +618,9 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
   constexpr int kAOct = kBK * C::BM / 8 / kThreads;  // pre-split A octets per thread
   constexpr int kAU = kPreA ? kAOct : C::kAQuads;    // A load units
   floatx4 ra[SUB][C::kAQuads], rb[SUB][kRB];
-  floatx4 rs[SUB][kPreA ? kAOct : 1][3];  // pre-split A: the three planes of one octet
+  static_assert(LV == 0 || kEmu, "precision levels: split-bf16 configurations only");
+  constexpr int kPl = 3 - LV;  // planes of this level
+  floatx4 rs[SUB][kPreA ? kAOct : 1][kPl];  // pre-split A: this level's planes of one octet
 
   // N-major B columns of this thread (forward / bwd-data): a quad of adjacent columns when
   // the operand is read as 16-byte quads (1x1, planes of 4k pixels), else columns BN/4
@@ -669,14 +707,14 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
   // pre-split A: row (tid >> 2) + (threads / 4) i, k octet (tid & 3) -- 48 bytes at
   // (row * ceil(K/8) + k/8) * 48 (k0 and k_end are multiples of 8 within K; the octet past
   // a K that is not is zero-padded)
-  auto load_a_split = [&](int k0, int i, floatx4 (&v)[3]) {
+  auto load_a_split = [&](int k0, int i, floatx4 (&v)[kPl]) {
     const int k = k0 + 8 * (tid & 3);
     const int row = m0 + (tid >> 2) + (kThreads / 4) * i;
     const uint32_t off = row < M && k < k_end
                              ? static_cast<uint32_t>((row * ((K + 7) >> 3) + (k >> 3)) * 48)
                              : kOOB;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) v[p] = bload4(ar, off + 16 * p);
+    for (int p = 0; p < kPl; ++p) v[p] = bload4(ar, off + 16 * p);
   };
 
   auto load_b = [&](int k0, int i) -> floatx4 {
@@ -874,22 +912,22 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
             __bf16* p = reinterpret_cast<__bf16*>(aimg(buf, u)) +
                         emu_off<C::BM>(tid & 3, (tid >> 2) + (kThreads / 4) * i);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
+            for (int pl = 0; pl < kPl; ++pl)
               *reinterpret_cast<floatx4*>(p + pl * kBK * C::BM) = rs[u][i][pl];
           }
         } else {
 #pragma unroll
           for (int i = 0; i < C::kAQuads; ++i)
-            store_emu_quad<C::BM>(aimg(buf, u), ra[u][i], (tid >> 3) + (kThreads / 8) * i,
+            store_emu_quad<C::BM, LV>(aimg(buf, u), ra[u][i], (tid >> 3) + (kThreads / 8) * i,
                                   tid & 7);
         }
 #pragma unroll
         for (int i = 0; i < kRB; ++i) {
           if constexpr (kBK_major)
-            store_emu_quad<C::BN>(bimg(buf, u), rb[u][i], (tid >> 3) + (kThreads / 8) * i,
+            store_emu_quad<C::BN, LV>(bimg(buf, u), rb[u][i], (tid >> 3) + (kThreads / 8) * i,
                                   tid & 7);
           else
-            store_emu_quad<C::BN>(bimg(buf, u), rb[u][i], tid % C::BN, kq_of(i));
+            store_emu_quad<C::BN, LV>(bimg(buf, u), rb[u][i], tid % C::BN, kq_of(i));
         }
       }
       return;
@@ -914,7 +952,7 @@ __global__ __launch_bounds__(Cfg<CFG>::kThreads, Cfg<CFG>::kWavesPerSimd) void c
 
   auto run_stage = [&](const float* ai, const float* bi, auto&& between) {
     if constexpr (kEmu)
-      mfma_stage_emu<CFG>(acc, ai, bi, lane, wm, wn, between);
+      mfma_stage_emu<CFG, LV>(acc, ai, bi, lane, wm, wn, between);
     else
       mfma_stage<CFG, kBK_major>(acc, ai, bi, lane, wm, wn, between);
   };
@@ -1157,11 +1195,21 @@ void launch_cfg(const float* a, const float* b, const float* xm, float* out, flo
   const bool plain = g.taps == 1 && g.sh == 1 && g.sw == 1 && g.ph == 0 && g.pw == 0 &&
                      g.oh == 0 && g.ow == 0;
   const dim3 grid(mb * nb, zs, ps.count > 0 ? ps.count : 1), block(C::kThreads);
+  // the level in force picks the instance of a split-bf16 configuration (read here, at
+  // launch: a captured graph keeps the kernels it was captured with)
+  const int level = C::EMU ? conv_precision_level() : 0;
   auto go = [&](auto plain_c, auto pre_c) {
-    hipLaunchKernelGGL((conv_gemm_kernel<MODE, CFG, decltype(plain_c)::value,
-                                         decltype(pre_c)::value>),
-                       grid, block, 0, stream, a, b, xm, out, pmean, pm2, g, M, N, K, k_chunk,
-                       split_stride, accumulate ? 1 : 0, a_bytes, b_bytes, ps, tail);
+    auto run = [&](auto lv_c) {
+      hipLaunchKernelGGL((conv_gemm_kernel<MODE, CFG, decltype(plain_c)::value,
+                                           decltype(pre_c)::value, decltype(lv_c)::value>),
+                         grid, block, 0, stream, a, b, xm, out, pmean, pm2, g, M, N, K, k_chunk,
+                         split_stride, accumulate ? 1 : 0, a_bytes, b_bytes, ps, tail);
+    };
+    if constexpr (C::EMU) {
+      if (level == 1) return run(std::integral_constant<int, 1>{});
+      if (level == 2) return run(std::integral_constant<int, 2>{});
+    }
+    run(std::integral_constant<int, 0>{});
   };
   using T = std::true_type;
   using F = std::false_type;
@@ -1582,6 +1630,22 @@ int env_int(const char* name, int fallback) {
   const char* v = std::getenv(name);
   return v != nullptr && *v != 0 ? std::atoi(v) : fallback;
 }
+
+namespace {
+std::atomic<int> precision_level{0};
+thread_local int precision_pin = -1;
+}  // namespace
+
+int conv_precision(int level) {
+  if (level > 2) throw std::runtime_error("conv_precision: level 0 (highest), 1 (high) or 2 (medium)");
+  if (level >= 0) precision_level.store(level);
+  return precision_level.load();
+}
+
+int conv_precision_level() { return precision_pin >= 0 ? precision_pin : precision_level.load(); }
+
+ConvPrecisionPin::ConvPrecisionPin(int level) : saved_(precision_pin) { precision_pin = level; }
+ConvPrecisionPin::~ConvPrecisionPin() { precision_pin = saved_; }
 
 bool conv_gemm_emu_cfg(int cfg) { return cfg >= kFirstEmuCfg && cfg < kConvGemmCfgs; }
 

@@ -131,6 +131,9 @@ ConvGemmPlan tuned_plan_raw(int mode, const float* a, const float* b, const floa
   hipEventCreate(&t1);
   ConvGemmPlan best = heuristic;
   float best_ms = -1.f;
+  // candidates are timed at `highest`: the table's content does not depend on the precision
+  // level in force when a shape is first seen
+  const ConvPrecisionPin at_highest(0);
   for (const auto& cand : conv_gemm_candidates(mode, g)) {
     float ms = 0.f;
     for (int rep = 0; rep < 2; ++rep) {  // first run: warm-up (code object, caches)
@@ -994,7 +997,11 @@ bool lib_dgrad_chosen(const ConvGemmGeo& g, const at::Tensor& like, Ours&& ours,
     }
     return best;
   };
-  const float ours_ms = time(ours);
+  float ours_ms;
+  {
+    const ConvPrecisionPin at_highest(0);  // (the choice is the same at every precision level)
+    ours_ms = time(ours);
+  }
   const float lib_ms = time(lib);
   hipEventDestroy(t0);
   hipEventDestroy(t1);
@@ -1867,6 +1874,9 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
   m.def("lib_dgrad_import(str text) -> int", &tgpipe::lib_dgrad_import);
   m.def("lib_dgrad_force(int mode) -> ()", &tgpipe::lib_dgrad_force);
   m.def("conv_gemm_force_cfg(int cfg, int splits=1) -> ()", &tgpipe::conv_gemm_force_cfg);
+  m.def("conv_precision(int level=-1) -> int", [](int64_t level) -> int64_t {
+    return tgpipe::conv_precision(static_cast<int>(std::min<int64_t>(level, 3)));
+  });
   m.def("conv_gemm_presplit(int budget_mb, bool clear=True) -> int", &tgpipe::conv_gemm_presplit);
   m.def("conv_gemm_presplit_refresh(Tensor[] sources) -> int",
         &tgpipe::conv_gemm_presplit_refresh);

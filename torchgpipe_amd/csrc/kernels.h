@@ -248,6 +248,25 @@ void launch_conv_gemm(int mode, const float* a, const float* b, const float* x_m
 // launch_slab_flush sums the slices into the gradient once per step.
 // Whether a plan's tile config runs on the split-bf16 MFMA (and so can take a pre-split A).
 bool conv_gemm_emu_cfg(int cfg);
+// Process-wide fp32 precision of the split-bf16 kernels (conv_gemm.hip CFG 7-11,
+// winograd_f4.hip bg_gemm_emu_kernel): 0 `highest` (six partial products, the default),
+// 1 `high` (hi.hi, hi.mid, mid.hi), 2 `medium` (hi.hi; the batched-GEMM Winograd kernel
+// runs `high` there).  conv_precision sets it when level >= 0 and returns the level in
+// force; the launch functions read conv_precision_level() when they pick the kernel
+// instance.  A ConvPrecisionPin holds the calling thread's launches at one level while it
+// lives (the find step times its candidates at `highest` whatever the level in force).
+int conv_precision(int level);
+int conv_precision_level();
+class ConvPrecisionPin {
+ public:
+  explicit ConvPrecisionPin(int level);
+  ~ConvPrecisionPin();
+  ConvPrecisionPin(const ConvPrecisionPin&) = delete;
+  ConvPrecisionPin& operator=(const ConvPrecisionPin&) = delete;
+
+ private:
+  int saved_;
+};
 // The A operand of a forward / backward-data GEMM (M x K row-major: W[co][ci*T], or with
 // `transposed` A[ci][co*T + t] = W[co][ci][t], T = taps) split into three bf16 planes,
 // [M][ceil(K/8)][3][8] (k octets, zero past K): 6 bytes per element, into `out`

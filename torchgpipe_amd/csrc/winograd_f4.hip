@@ -2122,7 +2122,13 @@ __global__ __launch_bounds__(256) void bg_input_f4_emu_kernel(const float* __res
 // BN columns as BN/32 tiles of v_mfma_f32_32x32x16_bf16, six MFMAs per tile and 16-deep
 // step.  A step's (128 + BN) x 96 bytes arrive by LDS-DMA (1 KiB pieces) into a three-slot
 // ring two steps ahead; the fragments of step k+1 are read while step k's MFMAs run.
-template <int BN>
+// kHigh (the reduced precision levels, conv_precision in kernels.h): the three products
+// without a lo part (hi.hi, hi.mid, mid.hi).  The lo plane's pieces of a step -- the last
+// third of each operand's pieces, as the planes lie one after the other -- are not fetched
+// into the ring and its fragments not read; the images in HBM keep all three planes.  Both
+// `high` and `medium` run this instance: hi.hi alone (2^-8 per product) is amplified by the
+// Winograd output transform beyond use.
+template <int BN, bool kHigh = false>
 __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
     const float* __restrict__ a, const float* __restrict__ bmat, float* __restrict__ c, int Mp,
     int Np, int ksteps, int mtiles, int ntiles, int batch, int splits) {
@@ -2132,6 +2138,13 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
   constexpr int kPer = (kPieces + kWaves - 1) / kWaves;
   constexpr int kNT = BN / 32;
   static_assert(BN % 32 == 0 && (96 * BN) % 1024 == 0 && kPer <= 8, "tile shape");
+  // planes fetched and read, the first MFMA kept, and the pieces of a step that carry them
+  constexpr int kPl = kHigh ? 2 : 3, kT0 = kHigh ? 3 : 0;
+  constexpr int kAKept = kAPieces * kPl / 3, kBKept = (kPieces - kAPieces) * kPl / 3;
+  static_assert(kAPieces % 3 == 0 && (kPieces - kAPieces) % 3 == 0, "a plane is whole pieces");
+  auto kept = [&](int piece) {
+    return piece < kAPieces ? piece < kAKept : piece - kAPieces < kBKept;
+  };
   __shared__ __attribute__((aligned(16))) char lds[3 * kStage];
 
   const int nwg = ntiles * mtiles * batch * splits;
@@ -2178,7 +2191,7 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const int piece = i * kWaves + wave;
-      if (piece < kPieces) {
+      if (piece < kPieces && kept(piece)) {
         const char* src = (piece < kAPieces ? abase + st * astep : bbase + st * bstep) +
                           src_off[i];
         __builtin_amdgcn_global_load_lds((glob_void_t*)src, (lds_void_t*)(dst + piece * 1024),
@@ -2186,7 +2199,13 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
       }
     }
   };
-  const int mine = (kPieces - wave + kWaves - 1) / kWaves;
+  int mine = (kPieces - wave + kWaves - 1) / kWaves;  // loads this wave issues per step
+  if constexpr (kHigh) {
+    mine = 0;
+#pragma unroll
+    for (int i = 0; i < kPer; ++i)
+      if (i * kWaves + wave < kPieces && kept(i * kWaves + wave)) ++mine;
+  }
   auto wait_stages_in_flight = [&](int k) {
     switch (k * mine) {
       case 0: bg_wait_vm<0>(); break;
@@ -2219,11 +2238,11 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
   // byte offsets of this lane's fragments in a slot: plane p at + p * 2 * rows * 16
   const int aoff = (h * BM + wave * 32 + l32) * 16;
   const int boff = kABytes + (h * BN + l32) * 16;
-  bf16x8 af[3], bf[3][kNT];
+  bf16x8 af[kPl], bf[kPl][kNT];
   auto fetch = [&](int buf) {
     const char* base = lds + buf * kStage;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < kPl; ++p) {
       af[p] = *reinterpret_cast<const bf16x8*>(base + aoff + p * 2 * BM * 16);
 #pragma unroll
       for (int j = 0; j < kNT; ++j)
@@ -2243,9 +2262,9 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
   constexpr int kPairs[6][2] = {{2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
   int buf = 0;
   for (int k = 0; k < nst; ++k) {
-    bf16x8 ac[3], bc[3][kNT];
+    bf16x8 ac[kPl], bc[kPl][kNT];
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < kPl; ++p) {
       ac[p] = af[p];
 #pragma unroll
       for (int j = 0; j < kNT; ++j) bc[p][j] = bf[p][j];
@@ -2259,7 +2278,7 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
       fetch(nb);
     }
 #pragma unroll
-    for (int t = 0; t < 6; ++t)
+    for (int t = kT0; t < 6; ++t)
 #pragma unroll
       for (int j = 0; j < kNT; ++j)
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ac[kPairs[t][0]], bc[kPairs[t][1]][j],
@@ -2276,6 +2295,17 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
     for (int r = 0; r < 16; ++r)
       cz[static_cast<int64_t>(m0 + (r & 3) + 8 * (r >> 2)) * Np + n] = acc[j][r];
   }
+}
+
+// The split-bf16 GEMM instance of the precision level in force (read at launch): every
+// reduced level runs the three `high` products.
+using BgEmuGemm = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
+BgEmuGemm bg_emu_gemm(int bn) {
+  if (conv_precision_level() != 0)
+    return bn == 64 ? bg_gemm_emu_kernel<64, true>
+           : bn == 96 ? bg_gemm_emu_kernel<96, true> : bg_gemm_emu_kernel<128, true>;
+  return bn == 64 ? bg_gemm_emu_kernel<64>
+         : bn == 96 ? bg_gemm_emu_kernel<96> : bg_gemm_emu_kernel<128>;
 }
 
 // Y = A^T (sum_z M[z]) A (+ bias): one thread per (output channel, tile), consecutive
@@ -3189,8 +3219,7 @@ void launch_bg_conv(const float* x, const float* a, const float* bias, float* y,
   using Gemm = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
   Gemm gemm = bg_gemm_kernel<4, 64, 2>;
   if (plan.emu) {
-    gemm = plan.bn == 64 ? bg_gemm_emu_kernel<64>
-           : plan.bn == 96 ? bg_gemm_emu_kernel<96> : bg_gemm_emu_kernel<128>;
+    gemm = bg_emu_gemm(plan.bn);
   } else switch (plan.waves * 10000 + plan.bn * 10 + plan.sub) {
     case 40481: gemm = bg_gemm_kernel<4, 48, 1>; break;
     case 40641: gemm = bg_gemm_kernel<4, 64, 1>; break;
@@ -3294,8 +3323,7 @@ void launch_wino4_wgrad_emu(const float* x, const float* dy, float* dw, float* w
   const int mtiles = static_cast<int>(p.mp / 128);
   const int ntiles = static_cast<int>(p.np / p.bn);
   const int64_t nwg = static_cast<int64_t>(mtiles) * ntiles * kP * splits;
-  auto gemm = p.bn == 64 ? bg_gemm_emu_kernel<64>
-              : p.bn == 96 ? bg_gemm_emu_kernel<96> : bg_gemm_emu_kernel<128>;
+  auto gemm = bg_emu_gemm(p.bn);
   hipLaunchKernelGGL(gemm, dim3(static_cast<unsigned>(nwg)), dim3(256), 0, stream, am, bv, cb,
                      static_cast<int>(p.mp), static_cast<int>(p.np), static_cast<int>(p.ksteps),
                      mtiles, ntiles, static_cast<int>(kP), splits);

@@ -35,6 +35,8 @@ def _load() -> None:
     try:
         importlib.import_module('torchgpipe_amd._C')
         _loaded = True
+        from torchgpipe_amd.ops import precision
+        precision._push()  # a level set before the extension was loaded
         db = os.environ.get('TGPIPE_CG_DB', SHIPPED_PLANS)
         if db != '0' and os.path.exists(db):
             load_plans(db)
@@ -49,10 +51,17 @@ def _load() -> None:
             _error = None
             importlib.import_module('torchgpipe_amd._C')
             _loaded = True
+            from torchgpipe_amd.ops import precision
+            precision._push()
 
 
 def available() -> bool:
     _load()
+    return _loaded
+
+
+def loaded() -> bool:
+    """Whether the extension is loaded already (never tries to load it)."""
     return _loaded
 
 
