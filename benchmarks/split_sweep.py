@@ -1,6 +1,6 @@
 """Split-K sweep of the F(4x4) weight-gradient and fused forward kernels.
 
-The host heuristics (``wino4_wgrad_splits`` / ``wino4_plan`` in csrc/winograd_f4.hip) ask
+The host heuristics (``wino4_wgrad_plan`` / ``wino4_plan`` in csrc/winograd_f4.hip) asked
 for >= 32 (weight gradient) / >= 16 (forward) reduction steps per split, which at
 ResNet-101's 15-36-image micro-batches leaves most of the 256 CUs idle (14^2 x 256
 channels at 22 images: 64 workgroups for 136 us, profiles/r5/rocprof/

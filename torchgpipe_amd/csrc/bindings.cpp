@@ -221,8 +221,7 @@ at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty({n, out_channels, h, w}, x.options());
   if (y.numel() == 0) return y;
-  TORCH_CHECK(variant == -1 || (variant >= 4 && variant <= 15 && variant != 11 && variant != 13) ||
-                  variant == 16 || variant == 17 || variant == 18 || (variant >= 20 && variant <= 22),
+  TORCH_CHECK(variant == -1 || wino4_variant_known(static_cast<int>(variant)),
               "variant must be -1, 4-10, 12, 14-18 or 20-22");
   const WinoPlan plan = wino4_plan(n, r, h, w, out_channels, static_cast<int>(variant),
                                    static_cast<int>(splits));
@@ -305,20 +304,13 @@ at::Tensor wino4_wgrad(const at::Tensor& x_in, const at::Tensor& dy_in, int64_t 
   TORCH_CHECK(variant >= 0 && variant <= 3,
               "variant must be 0 (fused), 1 (non-fused), 2 (split-bf16 batched GEMM) or 3 (fused, "
               "x rows through LDS)");
-  // every split owns >= 1 step (of 4 tiles; of 16 for the split-bf16 GEMM)
-  const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
-  const int64_t steps = variant == 2 ? (tiles + 15) / 16 : (tiles + 3) / 4;
-  const int s = static_cast<int>(std::min<int64_t>(
-      splits > 0 ? splits
-                 : (variant == 2 ? wino4_wgrad_emu_splits(n, c, k, h, w)
-                                 : wino4_wgrad_splits(n, c, k, h, w)),
-      steps));
-  const int64_t wsize = wino4_wgrad_workspace(n, c, k, h, w, s, static_cast<int>(variant));
+  const WinoPlan plan = wino4_wgrad_plan(n, c, k, h, w, static_cast<int>(variant),
+                                         static_cast<int>(splits));
   at::Tensor ws;
-  if (wsize > 0) ws = at::empty({wsize}, x.options());
+  if (plan.workspace > 0) ws = at::empty({plan.workspace}, x.options());
   launch_wino4_wgrad(x.data_ptr<float>(), dy.data_ptr<float>(), dw.data_ptr<float>(),
-                     wsize > 0 ? ws.data_ptr<float>() : nullptr, n, c, k, h, w, s,
-                     static_cast<int>(variant), accum, stream_of(x));
+                     plan.workspace > 0 ? ws.data_ptr<float>() : nullptr, n, c, k, h, w, plan,
+                     accum, stream_of(x));
   return dw;
 }
 
@@ -401,11 +393,37 @@ int64_t bg_stats_images(int64_t n, int64_t h, int64_t w, int64_t kind) {
 // Split-K count of the F(4x4) kernels for one convolution: variant 0 = the weight gradient,
 // otherwise that forward / backward-data variant (wino4_plan).
 int64_t wino4_splits(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int64_t variant) {
-  if (variant == 0) {
-    const int64_t steps = (n * ((h + 3) / 4) * ((w + 3) / 4) + 3) / 4;
-    return std::min<int64_t>(wino4_wgrad_splits(n, c, k, h, w), steps);
-  }
+  if (variant == 0) return wino4_wgrad_plan(n, c, k, h, w, 0, 0).splits;
   return wino4_plan(n, c, h, w, k, static_cast<int>(variant), 0).splits;
+}
+
+// The host plans as integer lists (no tensors, no device calls; tests/ops/
+// test_winograd_plans.py): c = reduction (input) channels, k = output channels.
+// [variant that runs, og, splits, workspace floats]
+std::vector<int64_t> wino4_plan_info(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w,
+                                     int64_t variant, int64_t splits) {
+  const WinoPlan p = wino4_plan(n, c, h, w, k, static_cast<int>(variant),
+                                static_cast<int>(splits));
+  return {p.variant, p.og, p.splits, p.workspace};
+}
+
+// [variant that runs, splits, workspace floats]
+std::vector<int64_t> wino4_wgrad_plan_info(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w,
+                                           int64_t variant, int64_t splits) {
+  const WinoPlan p = wino4_wgrad_plan(n, c, k, h, w, static_cast<int>(variant),
+                                      static_cast<int>(splits));
+  return {p.variant, p.splits, p.workspace};
+}
+
+// [kind, emu, waves, bn, sub, splits, ksteps, mp, np, workspace floats]
+std::vector<int64_t> bg_plan_info(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w,
+                                  int64_t bn, int64_t splits, int64_t kind, int64_t waves,
+                                  int64_t sub, int64_t emu) {
+  const BgPlan p = bg_plan(n, c, h, w, k, static_cast<int>(bn), static_cast<int>(splits),
+                           static_cast<int>(kind), static_cast<int>(waves),
+                           static_cast<int>(sub), static_cast<int>(emu));
+  return {p.kind, p.emu ? 1 : 0, p.waves, p.bn, p.sub, p.splits, p.ksteps, p.mp, p.np,
+          p.workspace};
 }
 
 }  // namespace
@@ -434,6 +452,13 @@ TORCH_LIBRARY(tgpipe, m) {
         &tgpipe::wino4_splits);
   m.def("bg_conv(Tensor x, Tensor a, Tensor? bias, int out_channels, int bn=0, int splits=0, "
         "int kind=4, int waves=0, int sub=0, int emu=-1, Tensor(b!)? stats=None) -> Tensor");
+  // the F(4x4) / batched-GEMM host plans (host only, CPU-testable)
+  m.def("wino4_plan_info(int n, int c, int k, int h, int w, int variant, int splits) -> int[]",
+        &tgpipe::wino4_plan_info);
+  m.def("wino4_wgrad_plan_info(int n, int c, int k, int h, int w, int variant, int splits) "
+        "-> int[]", &tgpipe::wino4_wgrad_plan_info);
+  m.def("bg_plan_info(int n, int c, int k, int h, int w, int bn, int splits, int kind, "
+        "int waves, int sub, int emu) -> int[]", &tgpipe::bg_plan_info);
   // images per BatchNorm-statistics group of bg_conv's `stats` (host only)
   m.def("bg_stats_images(int n, int h, int w, int kind) -> int", &tgpipe::bg_stats_images);
 }

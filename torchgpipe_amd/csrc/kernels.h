@@ -59,9 +59,10 @@ void launch_wino_weight(const float* w, float* u, int64_t out_channels, int64_t 
 // double-buffered, one workgroup per CU) and the
 // number of reduction splits (> 1 needs a workspace of `workspace` floats).
 struct WinoPlan {
-  int variant = 0;
+  int variant = 0;        // the variant that runs (a fallback's id where it replaces the asked one)
   int splits = 1;
   int64_t workspace = 0;
+  int og = 0;             // wino4_plan only: 16-channel output groups per workgroup (4 or 2)
 };
 WinoPlan wino_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                    int variant, int splits);
@@ -72,17 +73,18 @@ void launch_wino_conv(const float* x, const float* u, const float* bias, float* 
 
 // Winograd F(4x4,3x3) (winograd_f4.hip): same convolution, 36 MFMA multiplies per 16
 // output pixels.  Transformed weights U4[Rp4/4][Op4/16][4][16][36] (Rp4 = multiple of 4,
-// Op4 = multiple of 64).  Variant 4: 64 output channels x 32 tiles per 8-wave workgroup
-// (one per CU); variant 5: 32 x 32 per 4-wave workgroup (two per CU); 6 / 7: the same with
-// the weight slab by LDS-DMA; 14 / 15: non-fused (input-transform pass, then a GEMM with
-// both operands by LDS-DMA; the plan's workspace then includes V); 8-10: timing
-// ablations; 12: 6 with 16-byte patch rows; -1: auto (5).
+// Op4 = multiple of 64).  The variants (4-10, 12, 14-18, 20-22) are the rows of
+// winograd_f4.hip's kF4Variants, described in that file's header comment.  wino4_plan
+// resolves the id that runs (an unknown id or -1: 5; a row-staged variant whose width
+// precondition fails: its fallback), the split-K count and the workspace, which for the
+// non-fused 14 / 15 holds V ahead of the split partials.
 // wino4_supported(): input < 1 GiB etc.
 int64_t wino4_pad_reduction(int64_t r);
 int64_t wino4_pad_output(int64_t o);
 bool wino4_supported(int64_t n, int64_t r, int64_t h, int64_t w, int64_t o);
 void launch_wino4_weight(const float* w, float* u, int64_t out_channels, int64_t red_channels,
                          bool flip, hipStream_t stream);
+bool wino4_variant_known(int variant);
 WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                     int variant, int splits);
 void launch_wino4_conv(const float* x, const float* u, const float* bias, float* y, float* ws,
@@ -124,24 +126,18 @@ void launch_bg_conv(const float* x, const float* a, const float* bias, float* y,
 
 // F(4x4,3x3) weight gradient (winograd_f4.hip): dw[K][C][3][3], 36 MFMA multiplies per
 // 16 output pixels of each (k, c) pair; 64 k x 32 c per 8-wave workgroup, tiles split
-// over `splits` workgroups (> 1 needs a workspace of splits*K*C*9 floats).
+// over `splits` workgroups.  variant 0: fused (patch / gradient-tile staging inside the
+// GEMM kernel); 1: non-fused (transform passes into the GEMM's LDS image order, then an
+// LDS-DMA GEMM); 2: the split-bf16 batched GEMM; 3: 0 with the x rows staged through LDS.
+// wino4_wgrad_plan resolves the variant that runs (3 becomes 0 unless W % 4 == 0 and
+// W >= 16), the split count (`splits` > 0, else each variant's model; every split owns
+// >= 1 step) and the workspace: the split-K partials and the transformed operands of 1 / 2.
 bool wino4_wgrad_supported(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w);
-int wino4_wgrad_splits(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w);
-// variant 2: the split-bf16 batched-GEMM weight gradient (its own split count / workspace)
-int wino4_wgrad_emu_splits(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w);
-int64_t wino4_wgrad_emu_workspace(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w,
-                                  int splits);
-void launch_wino4_wgrad_emu(const float* x, const float* dy, float* dw, float* ws, int64_t n,
-                            int64_t c, int64_t k, int64_t h, int64_t w, int splits, bool accum,
-                            hipStream_t stream);
-// variant 0: fused (patch / gradient-tile staging inside the GEMM kernel); 1: non-fused
-// (transform passes into the GEMM's LDS image order, then an LDS-DMA GEMM).  The workspace
-// holds the split-K partials (splits > 1) and, for variant 1, the transformed operands.
-int64_t wino4_wgrad_workspace(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int splits,
-                              int variant);
+WinoPlan wino4_wgrad_plan(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int variant,
+                          int splits);
 // accum: add into dw (an existing gradient) instead of overwriting it.
 void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, int64_t n,
-                        int64_t c, int64_t k, int64_t h, int64_t w, int splits, int variant,
+                        int64_t c, int64_t k, int64_t h, int64_t w, const WinoPlan& plan,
                         bool accum, hipStream_t stream);
 
 // Weight gradient of the same convolution: dw[K][C][3][3] from x[N][C][H][W] and

@@ -22,18 +22,28 @@
 // order puts one patch wave and one slab wave on two of the four SIMDs and slab waves
 // on the other two, so no SIMD carries two transform streams.
 //
-// Forward / backward-data variants (host `variant`, ops/conv.py picks):
+// Forward / backward-data variants (host `variant`, ops/conv.py picks; one row each in
+// kF4Variants, which the plan, the launch and the binding's check read):
 //    4 / 5   fused, weight slab staged through registers (64 / 32 output channels)
 //    6 / 7   fused, weight slab by LDS-DMA (global_load_lds_dwordx4)      <- < 512 channels
-//   14 / 15  non-fused: f4_input_transform_kernel writes V in the GEMM's LDS-image order,
-//            f4_gemm_kernel copies both operands by LDS-DMA               <- >= 512 channels
-//    8-10    timing ablations of the fused patch staging (wrong results)
-//   12       6 with 16-byte patch-row loads
-//   16       6 with the raw input rows staged through LDS (W % 4 == 0; else runs as 6)
-//   17       7 with the same ring (measured slower than 7; not selected)
-//   20-22    timing ablations of variant 16 (wrong results)
-// Weight gradient: f4_wgrad_kernel (fused; f4_wgrad_rows_kernel: the same with the x rows
-// staged through LDS, wino4_wgrad variant 3) and f4_wg_vx/_mdy + f4_wgrad_gemm (non-fused).
+//    8-10    timing ablations of 6's patch staging (wrong results)
+//   12       6 with 16-byte patch-row loads (W % 4 == 0; else 6's kernel)
+//   14 / 15  non-fused (64 / 32 output channels): f4_input_transform_kernel writes V in the
+//            GEMM's LDS-image order, f4_gemm_kernel copies both operands by LDS-DMA
+//                                                                         <- >= 512 channels
+//   16       6 with the raw input rows staged through a two-slot LDS ring
+//            (f4_conv_rows_kernel; W % 4 == 0 and W >= 8, else runs as 6)  <- W >= 24
+//   17       7 with the same row ring, one workgroup per CU (W % 4 == 0 and W >= 24, else
+//            runs as 7; measured slower than 7, not selected)
+//   18       6 with the weight slab two steps ahead in a three-image LDS ring
+//            (f4_conv_ring_kernel; TGPIPE_F4_FUSED_VARIANT=18)
+//   20-22    timing ablations of 16 (wrong results; W % 4 == 0 and W >= 24, else run as 6)
+// Weight-gradient variants (wino4_wgrad_plan):
+//    0       fused, f4_wgrad_kernel
+//    1       non-fused: f4_wg_vx / f4_wg_mdy transform passes, then f4_wgrad_gemm_kernel
+//    2       split-bf16 batched GEMM (wg_*_emu transform passes, bg_gemm_emu_kernel)
+//    3       0 with the x rows staged through LDS, f4_wgrad_rows_kernel (W % 4 == 0 and
+//            W >= 16, else runs as 0)
 //
 // Padding taps (image borders, tiles past the end) are raw buffer loads with an
 // out-of-range offset: the hardware returns 0, so no select sits between a load and
@@ -1774,25 +1784,28 @@ __global__ __launch_bounds__(256) void bg_input_f4_kernel(const float* __restric
     *reinterpret_cast<floatx4*>(dst + b * plane) = floatx4{out[0][b], out[1][b], out[2][b], out[3][b]};
 }
 
-template <int N>
-__device__ __forceinline__ void bg_wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if constexpr (N == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-  else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-  else if constexpr (N == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+// s_waitcnt vmcnt(min(n, 16)) for a wave-uniform runtime n (the instruction takes an
+// immediate)
+__device__ __forceinline__ void bg_wait_vm(int n) {
+  switch (n) {
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
+    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
+    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
+    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
+    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
+  }
 }
 
 // C[z][b][Mp][Np] = sum over the split's steps of A[b]^T B[b].  Workgroup: kWaves waves, a
@@ -1862,27 +1875,7 @@ __global__ __launch_bounds__(64 * kWaves, 512 / (64 * kWaves)) void bg_gemm_kern
   // this wave's pieces per stage: waiting for vmcnt <= k * mine leaves the last k issued
   // stages in flight
   const int mine = (kPieces - wave + kWaves - 1) / kWaves;
-  auto wait_stages_in_flight = [&](int k) {
-    switch (k * mine) {
-      case 0: bg_wait_vm<0>(); break;
-      case 1: bg_wait_vm<1>(); break;
-      case 2: bg_wait_vm<2>(); break;
-      case 3: bg_wait_vm<3>(); break;
-      case 4: bg_wait_vm<4>(); break;
-      case 5: bg_wait_vm<5>(); break;
-      case 6: bg_wait_vm<6>(); break;
-      case 7: bg_wait_vm<7>(); break;
-      case 8: bg_wait_vm<8>(); break;
-      case 9: bg_wait_vm<9>(); break;
-      case 10: bg_wait_vm<10>(); break;
-      case 11: bg_wait_vm<11>(); break;
-      case 12: bg_wait_vm<12>(); break;
-      case 13: bg_wait_vm<13>(); break;
-      case 14: bg_wait_vm<14>(); break;
-      case 15: bg_wait_vm<15>(); break;
-      default: bg_wait_vm<16>(); break;
-    }
-  };
+  auto wait_stages_in_flight = [&](int k) { bg_wait_vm(k * mine); };
 
   floatx4 acc[2][kNJ];
 #pragma unroll
@@ -2206,27 +2199,7 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
     for (int i = 0; i < kPer; ++i)
       if (i * kWaves + wave < kPieces && kept(i * kWaves + wave)) ++mine;
   }
-  auto wait_stages_in_flight = [&](int k) {
-    switch (k * mine) {
-      case 0: bg_wait_vm<0>(); break;
-      case 1: bg_wait_vm<1>(); break;
-      case 2: bg_wait_vm<2>(); break;
-      case 3: bg_wait_vm<3>(); break;
-      case 4: bg_wait_vm<4>(); break;
-      case 5: bg_wait_vm<5>(); break;
-      case 6: bg_wait_vm<6>(); break;
-      case 7: bg_wait_vm<7>(); break;
-      case 8: bg_wait_vm<8>(); break;
-      case 9: bg_wait_vm<9>(); break;
-      case 10: bg_wait_vm<10>(); break;
-      case 11: bg_wait_vm<11>(); break;
-      case 12: bg_wait_vm<12>(); break;
-      case 13: bg_wait_vm<13>(); break;
-      case 14: bg_wait_vm<14>(); break;
-      case 15: bg_wait_vm<15>(); break;
-      default: bg_wait_vm<16>(); break;
-    }
-  };
+  auto wait_stages_in_flight = [&](int k) { bg_wait_vm(k * mine); };
 
   floatx16 acc[kNT];
 #pragma unroll
@@ -2295,17 +2268,6 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
     for (int r = 0; r < 16; ++r)
       cz[static_cast<int64_t>(m0 + (r & 3) + 8 * (r >> 2)) * Np + n] = acc[j][r];
   }
-}
-
-// The split-bf16 GEMM instance of the precision level in force (read at launch): every
-// reduced level runs the three `high` products.
-using BgEmuGemm = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
-BgEmuGemm bg_emu_gemm(int bn) {
-  if (conv_precision_level() != 0)
-    return bn == 64 ? bg_gemm_emu_kernel<64, true>
-           : bn == 96 ? bg_gemm_emu_kernel<96, true> : bg_gemm_emu_kernel<128, true>;
-  return bn == 64 ? bg_gemm_emu_kernel<64>
-         : bn == 96 ? bg_gemm_emu_kernel<96> : bg_gemm_emu_kernel<128>;
 }
 
 // Y = A^T (sum_z M[z]) A (+ bias): one thread per (output channel, tile), consecutive
@@ -2817,19 +2779,82 @@ void launch_wino4_weight(const float* w, float* u, int64_t out_channels, int64_t
                      flip);
 }
 
+namespace {
+
+// Split-K count <= max_splits (and <= steps) of the least modelled time: `blocks`
+// workgroups per split run in rounds of `wg_per_round`, a workgroup's `steps` are divided
+// among the splits at `step_us` each, and splitting at all adds a reduce pass of `pass_us`
+// plus `split_mb_us` per split and MB of partials (`mb` per split).
+int64_t split_k_by_cost(int64_t blocks, int64_t steps, int64_t wg_per_round, double step_us,
+                        double pass_us, double split_mb_us, double mb, int64_t max_splits) {
+  int64_t best = 1;
+  double best_cost = 0;
+  for (int64_t s = 1; s <= std::min(max_splits, steps); ++s) {
+    const int64_t rounds = (blocks * s + wg_per_round - 1) / wg_per_round;
+    const double cost = rounds * ((steps + s - 1) / s) * step_us +
+                        (s > 1 ? pass_us + split_mb_us * s * mb : 0.0);
+    if (s == 1 || cost < best_cost) {
+      best = s;
+      best_cost = cost;
+    }
+  }
+  return best;
+}
+
+// The forward / backward-data variants (the header comment describes them): one row per
+// host id.  All fused kernels share a signature and launch with 128 * og threads.
+using F4ConvKernel = void (*)(const float*, const float*, const float*, float*, int, int, int,
+                              int, int, int, int, int, int, int, int, int, uint32_t);
+struct F4Variant {
+  int id;
+  int og;                // 16-channel output groups of a workgroup: 4 (8 waves) or 2 (4 waves)
+  F4ConvKernel kernel;   // the fused kernel; nullptr: non-fused (f4_input_transform_kernel,
+                         // then f4_gemm_kernel<og>, V in the workspace ahead of the partials)
+  F4ConvKernel vec;      // taken instead where W % 4 == 0 (16-byte centre loads), if any
+  F4ConvKernel narrow;   // taken instead below 6 tiles per row, if any
+  int min_w;             // > 0: needs W % 4 == 0 and W >= min_w, ...
+  int fallback;          // ... and runs as this id otherwise
+};
+// 16-byte centre loads pay off in the 4-wave variants only: the 8-wave one ran 4-16 % slower
+// with them (12 against 6; benchmarks/wino_variants.py, profiles/wino_f4_variants.json), so
+// 18 has no `vec` either.  The row-staged kernels take whole 16-byte chunks; 16 has <= 7 row
+// segments per workgroup from 6 tiles per row on and <= 17 from 2, the 32-channel ring (17)
+// and the ablations (20-22) exist as the 7-segment instance only.
+constexpr F4Variant kF4Variants[] = {
+    {4, 4, f4_conv_kernel<4, false>, nullptr, nullptr, 0, 0},
+    {5, 2, f4_conv_kernel<2, false>, f4_conv_kernel<2, true>, nullptr, 0, 0},
+    {6, 4, f4_conv_kernel<4, false, true>, nullptr, nullptr, 0, 0},
+    {7, 2, f4_conv_kernel<2, false, true>, f4_conv_kernel<2, true, true>, nullptr, 0, 0},
+    {8, 4, f4_conv_kernel<4, false, true, 1>, nullptr, nullptr, 0, 0},
+    {9, 4, f4_conv_kernel<4, false, true, 2>, nullptr, nullptr, 0, 0},
+    {10, 4, f4_conv_kernel<4, false, true, 3>, nullptr, nullptr, 0, 0},
+    {12, 4, f4_conv_kernel<4, false, true>, f4_conv_kernel<4, true, true>, nullptr, 0, 0},
+    {14, 4, nullptr, nullptr, nullptr, 0, 0},
+    {15, 2, nullptr, nullptr, nullptr, 0, 0},
+    {16, 4, f4_conv_rows_kernel<46, 3>, nullptr, f4_conv_rows_kernel<66, 5>, 8, 6},
+    {17, 2, f4_conv_rows_kernel<46, 9, 2>, nullptr, nullptr, 24, 7},
+    {18, 4, f4_conv_ring_kernel<false>, nullptr, nullptr, 0, 0},
+    {20, 4, f4_conv_rows_kernel<46, 3, 4, 8>, nullptr, nullptr, 24, 6},
+    {21, 4, f4_conv_rows_kernel<46, 3, 4, 1>, nullptr, nullptr, 24, 6},
+    {22, 4, f4_conv_rows_kernel<46, 3, 4, 7>, nullptr, nullptr, 24, 6},
+};
+const F4Variant* f4_variant(int id) {
+  for (const F4Variant& v : kF4Variants)
+    if (v.id == id) return &v;
+  return nullptr;
+}
+}  // namespace
+
+bool wino4_variant_known(int variant) { return f4_variant(variant) != nullptr; }
+
 WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                     int variant, int splits) {
+  const F4Variant* v = f4_variant(variant);
+  if (v == nullptr) v = f4_variant(5);  // an unknown id, -1 (auto)
+  if (v->min_w > 0 && ((w & 3) != 0 || w < v->min_w)) v = f4_variant(v->fallback);
   WinoPlan plan;
-  plan.variant = (variant >= 4 && variant <= 12 && variant != 11) || variant == 14 ||
-                         variant == 15 || variant == 16 || variant == 17 || variant == 18 ||
-                         (variant >= 20 && variant <= 22) ? variant : 5;
-  // the row-staged kernel takes whole 16-byte chunks and at most 17 row segments
-  if (plan.variant == 16 && ((w & 3) != 0 || w < 8)) plan.variant = 6;
-  // the 32-channel ring and the ablations: the 7-segment instance only
-  if (plan.variant == 17 && ((w & 3) != 0 || w < 24)) plan.variant = 7;
-  if (plan.variant >= 20 && plan.variant <= 22 && ((w & 3) != 0 || w < 24)) plan.variant = 6;
-  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ||
-                         plan.variant == 17 ? 2 : 4;
+  plan.variant = v->id;
+  const int og = plan.og = v->og;
   const int64_t P = n * ((h + 3) / 4) * ((w + 3) / 4);
   const int64_t blocks = ((P + kT - 1) / kT) * ((out_channels + 16 * og - 1) / (16 * og));
   const int64_t steps = wino4_pad_reduction(red_channels) / kC;
@@ -2841,24 +2866,12 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
     // 32-channel workgroups ~1.9 us, two per CU), and per extra split ~0.23 us per MB of
     // output partials plus ~11.6 us for the reduce pass.  (The old ">= 16 steps per split"
     // rule kept ResNet's 28^2 x 128 layers at 22 images on 2 splits: 49 -> 41 us at 3.)
-    const int64_t cap = og == 4 ? 256 : 512;
-    const double step_us = og == 4 ? 2.1 : 1.9;
     const double mb = static_cast<double>(n) * out_channels * h * w * 4 / 1e6;
-    int64_t best = 1;
-    double best_cost = 0;
-    for (int64_t s = 1; s <= std::min<int64_t>(64, steps); ++s) {
-      const int64_t rounds = (blocks * s + cap - 1) / cap;
-      const double cost = rounds * ((steps + s - 1) / s) * step_us +
-                          (s > 1 ? 11.6 + 0.23 * s * mb : 0.0);
-      if (s == 1 || cost < best_cost) {
-        best = s;
-        best_cost = cost;
-      }
-    }
-    plan.splits = static_cast<int>(best);
+    plan.splits = static_cast<int>(split_k_by_cost(blocks, steps, og == 4 ? 256 : 512,
+                                                   og == 4 ? 2.1 : 1.9, 11.6, 0.23, mb, 64));
   }
   plan.workspace = plan.splits > 1 ? plan.splits * n * out_channels * h * w : 0;
-  if (plan.variant == 14 || plan.variant == 15) {  // + the transformed input V4[P/32][Rp/4][4][32][36], first
+  if (v->kernel == nullptr) {  // + the transformed input V4[P/32][Rp/4][4][32][36], first
     plan.workspace += ((P + kT - 1) / kT) * kT * wino4_pad_reduction(red_channels) * kP;
   }
   return plan;
@@ -2871,168 +2884,41 @@ void launch_wino4_conv(const float* x, const float* u, const float* bias, float*
   const int64_t Op = wino4_pad_output(out_channels);
   const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
   const int64_t P = n * th * tw;
-  const int og = plan.variant == 5 || plan.variant == 7 || plan.variant == 15 ||
-                         plan.variant == 17 ? 2 : 4;
+  const F4Variant& v = *f4_variant(plan.variant);  // wino4_plan's: a row of the table
+  const int og = v.og;
   const int tblocks = static_cast<int>((P + kT - 1) / kT);
-  if (plan.variant == 18) {
-    const int oblocks4 = static_cast<int>((out_channels + 63) / 64);
-    const int64_t nwg4 = static_cast<int64_t>(tblocks) * oblocks4 * plan.splits;
-    auto kernel = f4_conv_ring_kernel<false>;  // (16-byte centre loads: see variant 12)
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg4)), dim3(512), 0, stream, x, u,
-                       bias, plan.splits > 1 ? ws : y, static_cast<int>(red_channels),
-                       static_cast<int>(h), static_cast<int>(w),
-                       static_cast<int>(out_channels), static_cast<int>(Rp),
-                       static_cast<int>(Op), static_cast<int>(th), static_cast<int>(tw),
-                       static_cast<int>(P), tblocks, oblocks4, plan.splits,
-                       static_cast<uint32_t>(n * red_channels * h * w * 4));
-    if (plan.splits > 1)
-      launch_split_reduce(ws, bias, y, n * out_channels * h * w, h * w,
-                          static_cast<int>(out_channels), plan.splits, stream);
-    return;
-  }
   const int oblocks = static_cast<int>((out_channels + 16 * og - 1) / (16 * og));
   const int splits = plan.splits;
   const int64_t nwg = static_cast<int64_t>(tblocks) * oblocks * splits;
-  if (plan.variant == 14 || plan.variant == 15) {
-    float* vbuf = ws;
-    const int64_t vtotal = static_cast<int64_t>(tblocks) * kT * Rp;  // threads
-    float* split_ws = ws + vtotal * kP;
+  const int64_t vtotal = static_cast<int64_t>(tblocks) * kT * Rp;  // V's rows (non-fused)
+  float* partials = v.kernel == nullptr ? ws + vtotal * kP : ws;
+  float* out = splits > 1 ? partials : y;
+  if (v.kernel == nullptr) {
     hipLaunchKernelGGL(f4_input_transform_kernel, dim3(static_cast<unsigned>((vtotal + 255) / 256)),
-                       dim3(256), 0, stream, x, vbuf, static_cast<int>(red_channels),
+                       dim3(256), 0, stream, x, ws, static_cast<int>(red_channels),
                        static_cast<int>(h), static_cast<int>(w), static_cast<int>(tw),
                        static_cast<int>(th * tw), static_cast<int>(P), static_cast<int>(Rp),
                        vtotal, static_cast<uint32_t>(n * red_channels * h * w * 4));
     auto gemm = og == 4 ? f4_gemm_kernel<4> : f4_gemm_kernel<2>;
-    hipLaunchKernelGGL(gemm, dim3(static_cast<unsigned>(nwg)), dim3(128 * og), 0, stream, vbuf, u,
-                       bias, splits > 1 ? split_ws : y, static_cast<int>(h), static_cast<int>(w),
+    hipLaunchKernelGGL(gemm, dim3(static_cast<unsigned>(nwg)), dim3(128 * og), 0, stream, ws, u,
+                       bias, out, static_cast<int>(h), static_cast<int>(w),
                        static_cast<int>(out_channels), static_cast<int>(Rp), static_cast<int>(Op),
                        static_cast<int>(th), static_cast<int>(tw), static_cast<int>(P), tblocks,
                        oblocks, splits);
-    if (splits > 1)
-      launch_split_reduce(split_ws, bias, y, n * out_channels * h * w, h * w,
-                          static_cast<int>(out_channels), splits, stream);
-    return;
-  }
-  // 16-byte centre loads (W % 4 == 0) pay off in the 4-wave variant only: the 8-wave one
-  // ran 4-16 % slower with them (benchmarks/wino_variants.py, profiles/wino_f4_variants.json)
-  const bool vec = (w & 3) == 0;
-  auto kernel = og == 4 ? f4_conv_kernel<4, false>
-                        : (vec ? f4_conv_kernel<2, true> : f4_conv_kernel<2, false>);
-  if (plan.variant == 6) kernel = f4_conv_kernel<4, false, true>;
-  if (plan.variant == 8) kernel = f4_conv_kernel<4, false, true, 1>;
-  if (plan.variant == 9) kernel = f4_conv_kernel<4, false, true, 2>;
-  if (plan.variant == 10) kernel = f4_conv_kernel<4, false, true, 3>;
-  if (plan.variant == 12) kernel = vec ? f4_conv_kernel<4, true, true> : f4_conv_kernel<4, false, true>;
-  if (plan.variant == 7) kernel = vec ? f4_conv_kernel<2, true, true> : f4_conv_kernel<2, false, true>;
-  // <= 7 row segments per workgroup from 6 tiles per row on, <= 17 from 2
-  if (plan.variant == 16) kernel = tw >= 6 ? f4_conv_rows_kernel<46, 3> : f4_conv_rows_kernel<66, 5>;
-  if (plan.variant == 17) kernel = f4_conv_rows_kernel<46, 9, 2>;
-  if (plan.variant == 20) kernel = f4_conv_rows_kernel<46, 3, 4, 8>;
-  if (plan.variant == 21) kernel = f4_conv_rows_kernel<46, 3, 4, 1>;
-  if (plan.variant == 22) kernel = f4_conv_rows_kernel<46, 3, 4, 7>;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(128 * og), 0, stream,
-                     x, u, bias, splits > 1 ? ws : y, static_cast<int>(red_channels),
-                     static_cast<int>(h), static_cast<int>(w), static_cast<int>(out_channels),
-                     static_cast<int>(Rp), static_cast<int>(Op), static_cast<int>(th),
-                     static_cast<int>(tw), static_cast<int>(P), tblocks, oblocks, splits,
-                     static_cast<uint32_t>(n * red_channels * h * w * 4));
-  if (splits > 1) {
-    launch_split_reduce(ws, bias, y, n * out_channels * h * w, h * w,
-                        static_cast<int>(out_channels), splits, stream);
-  }
-}
-
-bool wino4_wgrad_supported(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
-  const int64_t lim = (int64_t{1} << 30) - 64;
-  const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
-  return n * c * h * w * 4 < lim && n * k * h * w * 4 < lim && n * c * h * w > 0 &&
-         n * k * h * w > 0 && tiles + 64 < (int64_t{1} << 30);
-}
-
-int wino4_wgrad_splits(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
-  // Split-K by a cost model fitted to benchmarks/split_sweep.py (profiles/r5/
-  // split_sweep.json): one 8-wave workgroup per CU, ~2.5 us per 4-tile step, and per extra
-  // split ~0.8 us per MB of k x c x 36 partials (written, then summed by the reduce pass)
-  // plus ~5 us for that pass.  The old ">= 32 steps per split" rule left 3/4 of the CUs
-  // idle at ResNet's 15-36-image micro-batches (14^2 x 256 channels at 22 images: 139 ->
-  // 57 us).
-  const int64_t blocks = ((c + 31) / 32) * ((k + 63) / 64);
-  const int64_t steps = (n * ((h + 3) / 4) * ((w + 3) / 4) + 3) / 4;
-  const double mb = static_cast<double>(((c + 31) / 32) * 32) * (((k + 63) / 64) * 64) * 9 * 4 /
-                    1e6;
-  int best = 1;
-  double best_cost = 0;
-  for (int64_t s = 1; s <= std::min<int64_t>(512, steps); ++s) {
-    const int64_t rounds = (blocks * s + 255) / 256;
-    const double cost = rounds * ((steps + s - 1) / s) * 2.5 + (s > 1 ? 5.0 + 0.8 * s * mb : 0.0);
-    if (s == 1 || cost < best_cost) {
-      best = static_cast<int>(s);
-      best_cost = cost;
-    }
-  }
-  return best;
-}
-
-int64_t wino4_wgrad_workspace(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int splits,
-                              int variant) {
-  if (variant == 2) return wino4_wgrad_emu_workspace(n, c, k, h, w, splits);
-  int64_t total = splits > 1 ? splits * k * c * 9 : 0;
-  if (variant == 1) {
-    const int64_t ppad = ((n * ((h + 3) / 4) * ((w + 3) / 4) + 3) / 4) * 4;
-    total += ppad * (((c + 31) / 32) * 32 + ((k + 63) / 64) * 64) * kP;
-  }
-  return total;
-}
-
-void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, int64_t n,
-                        int64_t c, int64_t k, int64_t h, int64_t w, int splits, int variant,
-                        bool accum, hipStream_t stream) {
-  const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
-  const int64_t P = n * th * tw;
-  const int cblocks = static_cast<int>((c + 31) / 32);
-  const int kblocks = static_cast<int>((k + 63) / 64);
-  const int64_t nwg = static_cast<int64_t>(cblocks) * kblocks * splits;
-  const uint32_t x_bytes = static_cast<uint32_t>(n * c * h * w * 4);
-  const uint32_t dy_bytes = static_cast<uint32_t>(n * k * h * w * 4);
-  if (variant == 2) {
-    launch_wino4_wgrad_emu(x, dy, dw, ws, n, c, k, h, w, splits, accum, stream);
-    return;
-  }
-  float* partial = ws;
-  if (variant == 1) {
-    const int64_t nsteps = (P + 3) / 4;
-    const int64_t ppad = nsteps * 4;
-    float* vx = ws;
-    float* m = vx + ppad * cblocks * 32 * kP;
-    partial = m + ppad * kblocks * 64 * kP;
-    const int64_t vt = ppad * cblocks * 32, mt = ppad * kblocks * 64;
-    hipLaunchKernelGGL(f4_wg_vx_kernel, dim3(static_cast<unsigned>((vt + 255) / 256)), dim3(256), 0,
-                       stream, x, vx, static_cast<int>(n), static_cast<int>(c), static_cast<int>(h),
-                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
-                       static_cast<int>(ppad), cblocks, vt, x_bytes);
-    auto mk = (w & 3) == 0 ? f4_wg_mdy_kernel<true> : f4_wg_mdy_kernel<false>;
-    hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>((mt + 255) / 256)), dim3(256), 0, stream, dy,
-                       m, static_cast<int>(n), static_cast<int>(k), static_cast<int>(h),
-                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
-                       static_cast<int>(ppad), kblocks, mt, dy_bytes);
-    hipLaunchKernelGGL(f4_wgrad_gemm_kernel<>, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
-                       stream, vx, m, splits > 1 ? partial : dw, static_cast<int>(c),
-                       static_cast<int>(k), static_cast<int>(nsteps), cblocks, kblocks, splits,
-                       accum && splits == 1);
   } else {
-    auto kernel = (w & 3) == 0 ? f4_wgrad_kernel<true> : f4_wgrad_kernel<false>;
-    // variant 3 (row-staged x operand): whole 16-byte chunks, at most one row break per step
-    if (variant == 3 && (w & 3) == 0 && w >= 16) kernel = f4_wgrad_rows_kernel;
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
-                       stream, x, dy, splits > 1 ? partial : dw, static_cast<int>(n),
-                       static_cast<int>(c), static_cast<int>(k), static_cast<int>(h),
-                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
-                       static_cast<int>(P), cblocks, kblocks, splits, x_bytes, dy_bytes,
-                       accum && splits == 1);
+    F4ConvKernel kernel = v.kernel;
+    if (v.vec != nullptr && (w & 3) == 0) kernel = v.vec;
+    if (v.narrow != nullptr && tw < 6) kernel = v.narrow;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(128 * og), 0, stream, x, u,
+                       bias, out, static_cast<int>(red_channels), static_cast<int>(h),
+                       static_cast<int>(w), static_cast<int>(out_channels), static_cast<int>(Rp),
+                       static_cast<int>(Op), static_cast<int>(th), static_cast<int>(tw),
+                       static_cast<int>(P), tblocks, oblocks, splits,
+                       static_cast<uint32_t>(n * red_channels * h * w * 4));
   }
   if (splits > 1) {
-    launch_split_reduce(partial, nullptr, dw, k * c * 9, 9, static_cast<int>(k), splits, stream,
-                        accum);
+    launch_split_reduce(partials, bias, y, n * out_channels * h * w, h * w,
+                        static_cast<int>(out_channels), splits, stream);
   }
 }
 
@@ -3041,12 +2927,47 @@ void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, i
 namespace {
 constexpr int kBgRowPad = 256;  // weight rows (output channels) padded for either tile height
 int64_t bg_round(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-// (waves, BN) instantiations of bg_gemm_kernel
-constexpr int kBgTiles[][2] = {{4, 48}, {4, 64}, {4, 96}, {4, 128},
-                               {8, 64}, {8, 96}, {8, 128}, {8, 144}};
+// The instantiations of bg_gemm_kernel<waves, BN, sub>
+using BgGemm = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
+struct BgTile {
+  int waves, bn, sub;
+  BgGemm kernel;
+};
+constexpr BgTile kBgTiles[] = {
+    {4, 48, 1, bg_gemm_kernel<4, 48, 1>},   {4, 48, 2, bg_gemm_kernel<4, 48, 2>},
+    {4, 64, 1, bg_gemm_kernel<4, 64, 1>},   {4, 64, 2, bg_gemm_kernel<4, 64, 2>},
+    {4, 96, 1, bg_gemm_kernel<4, 96, 1>},   {4, 96, 2, bg_gemm_kernel<4, 96, 2>},
+    {4, 128, 1, bg_gemm_kernel<4, 128, 1>}, {4, 128, 2, bg_gemm_kernel<4, 128, 2>},
+    {8, 64, 1, bg_gemm_kernel<8, 64, 1>},   {8, 96, 1, bg_gemm_kernel<8, 96, 1>},
+    {8, 128, 1, bg_gemm_kernel<8, 128, 1>}, {8, 144, 1, bg_gemm_kernel<8, 144, 1>},
+};
+// The instantiations of the split-bf16 bg_gemm_emu_kernel<BN> (4 waves, one step per
+// stage): all six partial products (`highest`), or the three of `high` that every reduced
+// precision level runs.
+struct BgEmuTile {
+  int bn;
+  BgGemm highest, reduced;
+};
+constexpr BgEmuTile kBgEmuTiles[] = {
+    {64, bg_gemm_emu_kernel<64>, bg_gemm_emu_kernel<64, true>},
+    {96, bg_gemm_emu_kernel<96>, bg_gemm_emu_kernel<96, true>},
+    {128, bg_gemm_emu_kernel<128>, bg_gemm_emu_kernel<128, true>},
+};
+// The split-bf16 GEMM instance of the precision level in force (read at launch)
+BgGemm bg_emu_gemm(int bn) {
+  const BgEmuTile* tile = &kBgEmuTiles[2];  // a width outside the table: the widest
+  for (const BgEmuTile& t : kBgEmuTiles)
+    if (t.bn == bn) tile = &t;
+  return conv_precision_level() != 0 ? tile->reduced : tile->highest;
+}
 // 16-deep steps of the transformed operands: the reduction padded to 32 channels, so a
 // pipeline stage may hold one or two steps
 int64_t bg_ksteps(int64_t red_channels) { return (red_channels + 31) / 32 * 2; }
+// Floats of a transformed operand: [npos][ksteps][rows] of 16 floats, or of the 96 bytes
+// (24 floats' worth) of their split-bf16 image
+int64_t bg_image_numel(int64_t npos, int64_t ksteps, int64_t rows, bool emu) {
+  return npos * ksteps * (emu ? 24 : 16) * rows;
+}
 }  // namespace
 
 bool bg_emu(int emu) {
@@ -3090,21 +3011,17 @@ BgPlan bg_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t ou
   plan.ksteps = bg_ksteps(red_channels);
   plan.mp = bg_round(out_channels, kBgRowPad);
   bool valid = false;
-  for (const auto& t : kBgTiles) valid |= t[0] == waves && t[1] == bn;
-  if (plan.emu) {  // 4 waves x bn 64 / 96 / 128, one step per stage
-    valid = waves == 4 && (bn == 64 || bn == 96 || bn == 128);
+  if (plan.emu) {
+    for (const BgEmuTile& t : kBgEmuTiles) valid |= waves == 4 && t.bn == bn;
     sub = 1;
-    if (!valid) {
-      waves = 4;
-      bn = bg_pick_bn(P, plan.kind, true);
-      valid = true;
-    }
+  } else {
+    for (const BgTile& t : kBgTiles) valid |= t.waves == waves && t.bn == bn;
   }
   if (!valid) {
     // Auto: 128-row tiles (4 waves), which beat the 256-row ones on every measured U-Net
     // shape once the fragment reads were software-pipelined (profiles/r3/bg_bench.json)
     waves = 4;
-    bn = bg_pick_bn(P, plan.kind);
+    bn = bg_pick_bn(P, plan.kind, plan.emu);
   }
   plan.waves = waves;
   plan.bn = bn;
@@ -3126,34 +3043,28 @@ BgPlan bg_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t ou
   // every split owns >= 1 pipeline stage
   plan.splits = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(plan.splits,
                                                                         plan.ksteps / plan.sub)));
-  // (split-bf16 V: 24 floats' worth of bytes per row and step instead of 16)
-  plan.workspace = npos * plan.ksteps * (plan.emu ? 24 : 16) * plan.np +
+  plan.workspace = bg_image_numel(npos, plan.ksteps, plan.np, plan.emu) +
                    plan.splits * npos * plan.mp * plan.np;
   return plan;
 }
 
 int64_t bg_weight_numel(int64_t out_channels, int64_t red_channels, int kind, int emu) {
-  return (kind == 2 ? kP2 : kP) * bg_ksteps(red_channels) * (bg_emu(emu) ? 24 : 16) *
-         bg_round(out_channels, kBgRowPad);
+  return bg_image_numel(kind == 2 ? kP2 : kP, bg_ksteps(red_channels),
+                        bg_round(out_channels, kBgRowPad), bg_emu(emu));
 }
 
 void launch_bg_weight(const float* w, float* a, int64_t out_channels, int64_t red_channels,
                       bool flip, int kind, hipStream_t stream, int emu) {
   const int64_t mp = bg_round(out_channels, kBgRowPad);
   const int64_t ksteps = bg_ksteps(red_channels);
-  if (bg_emu(emu)) {
-    const int64_t total = ksteps * 4 * mp;
-    hipLaunchKernelGGL(kind == 2 ? bg_weight_f2_emu_kernel : bg_weight_f4_emu_kernel,
-                       dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, w,
-                       a, static_cast<int>(out_channels), static_cast<int>(red_channels),
-                       static_cast<int>(mp), static_cast<int>(ksteps), flip);
-    return;
-  }
-  const int64_t total = ksteps * 16 * mp;
-  hipLaunchKernelGGL(kind == 2 ? bg_weight_f2_kernel : bg_weight_f4_kernel,
-                     dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, w, a,
-                     static_cast<int>(out_channels), static_cast<int>(red_channels),
-                     static_cast<int>(mp), static_cast<int>(ksteps), flip);
+  const bool split = bg_emu(emu);
+  const int64_t total = ksteps * (split ? 4 : 16) * mp;
+  auto kernel = kind == 2 ? (split ? bg_weight_f2_emu_kernel : bg_weight_f2_kernel)
+                          : (split ? bg_weight_f4_emu_kernel : bg_weight_f4_kernel);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
+                     stream, w, a, static_cast<int>(out_channels),
+                     static_cast<int>(red_channels), static_cast<int>(mp),
+                     static_cast<int>(ksteps), flip);
 }
 
 int bg_stats_ipg(int64_t n, int64_t h, int64_t w, int kind) {
@@ -3172,7 +3083,7 @@ void launch_bg_conv(const float* x, const float* a, const float* bias, float* y,
   const int64_t th = (h + tile - 1) / tile, tw = (w + tile - 1) / tile;
   const int64_t P = n * th * tw;
   float* v = ws;
-  float* cbuf = ws + npos * plan.ksteps * (plan.emu ? 24 : 16) * plan.np;
+  float* cbuf = ws + bg_image_numel(npos, plan.ksteps, plan.np, plan.emu);
   const int64_t vt = plan.ksteps * 16 * plan.np;
   if (plan.emu) {
     // channels per thread: 4 (8-byte stores) while that fills the chip with >= 512
@@ -3216,24 +3127,12 @@ void launch_bg_conv(const float* x, const float* a, const float* bias, float* y,
   const int mtiles = static_cast<int>(plan.mp / (32 * plan.waves));
   const int ntiles = static_cast<int>(plan.np / plan.bn);
   const int64_t nwg = static_cast<int64_t>(mtiles) * ntiles * npos * plan.splits;
-  using Gemm = void (*)(const float*, const float*, float*, int, int, int, int, int, int, int);
-  Gemm gemm = bg_gemm_kernel<4, 64, 2>;
+  BgGemm gemm = bg_gemm_kernel<4, 64, 2>;
   if (plan.emu) {
     gemm = bg_emu_gemm(plan.bn);
-  } else switch (plan.waves * 10000 + plan.bn * 10 + plan.sub) {
-    case 40481: gemm = bg_gemm_kernel<4, 48, 1>; break;
-    case 40641: gemm = bg_gemm_kernel<4, 64, 1>; break;
-    case 40961: gemm = bg_gemm_kernel<4, 96, 1>; break;
-    case 41281: gemm = bg_gemm_kernel<4, 128, 1>; break;
-    case 40482: gemm = bg_gemm_kernel<4, 48, 2>; break;
-    case 40642: gemm = bg_gemm_kernel<4, 64, 2>; break;
-    case 40962: gemm = bg_gemm_kernel<4, 96, 2>; break;
-    case 41282: gemm = bg_gemm_kernel<4, 128, 2>; break;
-    case 80641: gemm = bg_gemm_kernel<8, 64, 1>; break;
-    case 80961: gemm = bg_gemm_kernel<8, 96, 1>; break;
-    case 81281: gemm = bg_gemm_kernel<8, 128, 1>; break;
-    case 81441: gemm = bg_gemm_kernel<8, 144, 1>; break;
-    default: break;
+  } else {
+    for (const BgTile& t : kBgTiles)
+      if (t.waves == plan.waves && t.bn == plan.bn && t.sub == plan.sub) gemm = t.kernel;
   }
   const int block = 64 * plan.waves;
   hipLaunchKernelGGL(gemm, dim3(static_cast<unsigned>(nwg)), dim3(block), 0, stream, a,
@@ -3279,33 +3178,30 @@ WgEmuPlan wg_emu_plan(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
   p.np = bg_round(c, p.bn);
   return p;
 }
-}  // namespace
 
-int wino4_wgrad_emu_splits(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+int wg_emu_splits(const WgEmuPlan& p) {
   // two workgroups per CU: >= 2 rounds over the 256 CUs, >= 8 sixteen-tile steps per split
-  const WgEmuPlan p = wg_emu_plan(n, c, k, h, w);
   const int64_t tiles = (p.mp / 128) * (p.np / p.bn) * kP;
   int64_t s = 1;
   while (tiles * s < 1024 && p.ksteps / (s * 2) >= 8) s *= 2;
   return static_cast<int>(s);
 }
 
-int64_t wino4_wgrad_emu_workspace(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w,
-                                  int splits) {
-  const WgEmuPlan p = wg_emu_plan(n, c, k, h, w);
-  // M' and V images (96 bytes = 24 floats per row and step), then the split partials
-  return kP * p.ksteps * 24 * (p.mp + p.np) + static_cast<int64_t>(splits) * kP * p.mp * p.np;
+int64_t wg_emu_workspace(const WgEmuPlan& p, int splits) {
+  // M' and V images, then the split partials
+  return bg_image_numel(kP, p.ksteps, p.mp + p.np, true) +
+         static_cast<int64_t>(splits) * kP * p.mp * p.np;
 }
 
-void launch_wino4_wgrad_emu(const float* x, const float* dy, float* dw, float* ws, int64_t n,
-                            int64_t c, int64_t k, int64_t h, int64_t w, int splits, bool accum,
-                            hipStream_t stream) {
+void launch_wgrad_emu(const float* x, const float* dy, float* dw, float* ws, int64_t n,
+                      int64_t c, int64_t k, int64_t h, int64_t w, int splits, bool accum,
+                      hipStream_t stream) {
   const WgEmuPlan p = wg_emu_plan(n, c, k, h, w);
   const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
   const int64_t P = n * th * tw;
   float* am = ws;
-  float* bv = am + kP * p.ksteps * 24 * p.mp;
-  float* cb = bv + kP * p.ksteps * 24 * p.np;
+  float* bv = am + bg_image_numel(kP, p.ksteps, p.mp, true);
+  float* cb = bv + bg_image_numel(kP, p.ksteps, p.np, true);
   const bool vec = (w & 3) == 0;
   const int64_t mt = p.ksteps * 4 * p.mp, vt = p.ksteps * 4 * p.np;
   hipLaunchKernelGGL(vec ? wg_dy_emu_kernel<true> : wg_dy_emu_kernel<false>,
@@ -3331,6 +3227,100 @@ void launch_wino4_wgrad_emu(const float* x, const float* dy, float* dw, float* w
   hipLaunchKernelGGL(wg_output_emu_kernel, dim3(static_cast<unsigned>((ot + 255) / 256)),
                      dim3(256), 0, stream, cb, dw, static_cast<int>(k), static_cast<int>(c),
                      static_cast<int>(p.mp), static_cast<int>(p.np), splits, accum);
+}
+}  // namespace
+
+// ---- weight gradient host side (variants 0-3) ---------------------------------------------
+
+bool wino4_wgrad_supported(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w) {
+  const int64_t lim = (int64_t{1} << 30) - 64;
+  const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
+  return n * c * h * w * 4 < lim && n * k * h * w * 4 < lim && n * c * h * w > 0 &&
+         n * k * h * w > 0 && tiles + 64 < (int64_t{1} << 30);
+}
+
+WinoPlan wino4_wgrad_plan(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int variant,
+                          int splits) {
+  WinoPlan plan;
+  plan.variant = variant >= 1 && variant <= 3 ? variant : 0;
+  // the row-staged x operand: whole 16-byte chunks, at most one row break per step
+  if (plan.variant == 3 && ((w & 3) != 0 || w < 16)) plan.variant = 0;
+  const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
+  const int64_t cpad = (c + 31) / 32 * 32, kpad = (k + 63) / 64 * 64;  // 32 c x 64 k blocks
+  const bool emu = plan.variant == 2;
+  const WgEmuPlan p = wg_emu_plan(n, c, k, h, w);
+  // every split owns >= 1 step (of 4 tiles; of 16 for the split-bf16 GEMM)
+  const int64_t steps = emu ? (tiles + 15) / 16 : (tiles + 3) / 4;
+  int64_t s = splits;
+  if (s <= 0 && emu) s = wg_emu_splits(p);
+  if (s <= 0) {
+    // Split-K by a cost model fitted to benchmarks/split_sweep.py (profiles/r5/
+    // split_sweep.json): one 8-wave workgroup per CU, ~2.5 us per 4-tile step, and per extra
+    // split ~0.8 us per MB of k x c x 36 partials (written, then summed by the reduce pass)
+    // plus ~5 us for that pass.  The old ">= 32 steps per split" rule left 3/4 of the CUs
+    // idle at ResNet's 15-36-image micro-batches (14^2 x 256 channels at 22 images: 139 ->
+    // 57 us).
+    const double mb = static_cast<double>(cpad) * kpad * 9 * 4 / 1e6;
+    s = split_k_by_cost((cpad / 32) * (kpad / 64), steps, 256, 2.5, 5.0, 0.8, mb, 512);
+  }
+  plan.splits = static_cast<int>(std::min(s, steps));
+  // the split-K partials, after the transformed operands of the non-fused variants
+  plan.workspace = plan.splits > 1 ? plan.splits * k * c * 9 : 0;
+  if (plan.variant == 1) plan.workspace += steps * 4 * (cpad + kpad) * kP;
+  if (emu) plan.workspace = wg_emu_workspace(p, plan.splits);
+  return plan;
+}
+
+void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, int64_t n,
+                        int64_t c, int64_t k, int64_t h, int64_t w, const WinoPlan& plan,
+                        bool accum, hipStream_t stream) {
+  const int splits = plan.splits;
+  if (plan.variant == 2) {
+    launch_wgrad_emu(x, dy, dw, ws, n, c, k, h, w, splits, accum, stream);
+    return;
+  }
+  const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
+  const int64_t P = n * th * tw;
+  const int cblocks = static_cast<int>((c + 31) / 32);
+  const int kblocks = static_cast<int>((k + 63) / 64);
+  const int64_t nwg = static_cast<int64_t>(cblocks) * kblocks * splits;
+  const uint32_t x_bytes = static_cast<uint32_t>(n * c * h * w * 4);
+  const uint32_t dy_bytes = static_cast<uint32_t>(n * k * h * w * 4);
+  float* partial = ws;
+  if (plan.variant == 1) {
+    const int64_t nsteps = (P + 3) / 4;
+    const int64_t ppad = nsteps * 4;
+    float* vx = ws;
+    float* m = vx + ppad * cblocks * 32 * kP;
+    partial = m + ppad * kblocks * 64 * kP;
+    const int64_t vt = ppad * cblocks * 32, mt = ppad * kblocks * 64;
+    hipLaunchKernelGGL(f4_wg_vx_kernel, dim3(static_cast<unsigned>((vt + 255) / 256)), dim3(256), 0,
+                       stream, x, vx, static_cast<int>(n), static_cast<int>(c), static_cast<int>(h),
+                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
+                       static_cast<int>(ppad), cblocks, vt, x_bytes);
+    auto mk = (w & 3) == 0 ? f4_wg_mdy_kernel<true> : f4_wg_mdy_kernel<false>;
+    hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>((mt + 255) / 256)), dim3(256), 0, stream, dy,
+                       m, static_cast<int>(n), static_cast<int>(k), static_cast<int>(h),
+                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
+                       static_cast<int>(ppad), kblocks, mt, dy_bytes);
+    hipLaunchKernelGGL(f4_wgrad_gemm_kernel<>, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
+                       stream, vx, m, splits > 1 ? partial : dw, static_cast<int>(c),
+                       static_cast<int>(k), static_cast<int>(nsteps), cblocks, kblocks, splits,
+                       accum && splits == 1);
+  } else {
+    auto kernel = (w & 3) == 0 ? f4_wgrad_kernel<true> : f4_wgrad_kernel<false>;
+    if (plan.variant == 3) kernel = f4_wgrad_rows_kernel;
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
+                       stream, x, dy, splits > 1 ? partial : dw, static_cast<int>(n),
+                       static_cast<int>(c), static_cast<int>(k), static_cast<int>(h),
+                       static_cast<int>(w), static_cast<int>(th), static_cast<int>(tw),
+                       static_cast<int>(P), cblocks, kblocks, splits, x_bytes, dy_bytes,
+                       accum && splits == 1);
+  }
+  if (splits > 1) {
+    launch_split_reduce(partial, nullptr, dw, k * c * 9, 9, static_cast<int>(k), splits, stream,
+                        accum);
+  }
 }
 
 }  // namespace tgpipe

@@ -341,10 +341,12 @@ def clear_winograd_caches(module: torch.nn.Module) -> None:
 # 6-pixel plane).  The F(4x4) kernel's 32-bit offsets need the input below 1 GiB.
 F4_MIN_PLANE = 8
 # Fused F(4x4) forward / backward-data kernel for < 512 channels: 16 (6 with the raw input
-# rows staged through LDS; runs as 6 where W % 4 != 0), 6 (slab one step ahead, per-tap
-# patch loads) or 18 (slab ring, two steps ahead; csrc/winograd_f4.hip).  16 is faster than
-# 6 on every U-Net shape from 24^2 up and no faster below (profiles/r9/f4_rows), so
-# narrower planes stay on 6.  TGPIPE_F4_FUSED_VARIANT.
+# rows staged through LDS; runs as 6 unless W % 4 == 0 and W >= 8), 6 (slab one step ahead,
+# per-tap patch loads) or 18 (slab ring, two steps ahead).  The ids are the rows of
+# kF4Variants in csrc/winograd_f4.hip (its header comment lists them all; wino4_plan
+# applies the width fallbacks).  16 is faster than 6 on every U-Net shape from 24^2 up and
+# no faster below (profiles/r9/f4_rows), so narrower planes stay on 6.
+# TGPIPE_F4_FUSED_VARIANT.
 _F4_FUSED_VARIANT = int(os.environ.get('TGPIPE_F4_FUSED_VARIANT', '16'))
 F4_ROWS_MIN_WIDTH = 24
 F4_MAX_BYTES = (1 << 30) - 64
@@ -569,8 +571,10 @@ WGRAD_EMU_MIN_TILES = 320
 
 
 def _wgrad_f4_variant(x: Tensor, weight: Tensor) -> int:
-    """F(4x4) weight-gradient kernel (benchmarks/wgrad_variants.py,
-    profiles/r5/wgrad_variants_emu.json): from 512 channels on both sides the non-fused
+    """F(4x4) weight-gradient variant (0 fused, 1 non-fused, 2 split-bf16 batched GEMM, 3
+    fused with the x rows through LDS: csrc/winograd_f4.hip's header comment;
+    wino4_wgrad_plan runs 3 as 0 below W = 16).  benchmarks/wgrad_variants.py,
+    profiles/r5/wgrad_variants_emu.json: from 512 channels on both sides the non-fused
     kernels (transform passes + GEMM; 11-23 % faster than the fused one there, 1.2-3.6x
     slower on the wide shallow planes, profiles/wgrad_f4_variants.json) -- the split-bf16
     batched GEMM (2) once the tile count amortises its products' trip through HBM
