@@ -77,7 +77,8 @@ def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument('--iters', type=int, default=20)
     p.add_argument('--out', default=None)
-    p.add_argument('--ops', default='wgrad,fwd', help="any of wgrad, fwd, bg")
+    p.add_argument('--ops', default='wgrad,fwd',
+                   help="any of wgrad, fwd, bg, emu (the fused split-bf16 forward, variant 24)")
     p.add_argument('--shape', type=int, nargs=4, action='append', default=None,
                    help='N C K H (repeatable; default: the built-in table)')
     a = p.parse_args()
@@ -88,7 +89,7 @@ def main() -> None:
             rows.append(bg_row(ops, n, c, k, h, a.iters))
             print(json.dumps(rows[-1]), flush=True)
     for n, c, k, h in (a.shape or SHAPES):
-        if 'wgrad' not in a.ops and 'fwd' not in a.ops:
+        if not any(op in a.ops for op in ('wgrad', 'fwd', 'emu')):
             break
         torch.manual_seed(0)
         x = torch.randn(n, c, h, h, device='cuda')
@@ -113,12 +114,13 @@ def main() -> None:
                         best = s
                 res['best'] = best
                 row[f'wgrad_v{var}'] = res
-        if 'fwd' in a.ops and h >= 8 and k < 256:
-            u = ops.wino4_weight(w, False)
-            steps = -(-c // 4)
+        if ('fwd' in a.ops or 'emu' in a.ops) and h >= 8 and k < 256:
             tiles = n * -(-h // 4) * -(-h // 4)
             blocks = -(-tiles // 32) * -(-k // 64)
-            for var in (6, 7):
+            for var in ((6, 7) if 'fwd' in a.ops else ()) + ((24,) if 'emu' in a.ops else ()):
+                # 24 divides 16-channel chunks of its own weight image among the splits
+                u = ops.wino4_weight_emu(w, False) if var == 24 else ops.wino4_weight(w, False)
+                steps = -(-c // 16) if var == 24 else -(-c // 4)
                 ref = ops.wino4_conv(x, u, None, k, var, 1).double()
                 res = {'auto': round(timed(lambda: ops.wino4_conv(x, u, None, k, var, 0),
                                            a.iters), 4)}

@@ -197,6 +197,29 @@ at::Tensor wino4_weight(const at::Tensor& w, bool flip, const c10::optional<at::
   return u;
 }
 
+// The weight image of the fused split-bf16 kernel (variant 24): bf16 hi and mid planes of
+// U as [Rp/16][Op/64][36 positions][4 KiB], Rp a multiple of 16.
+std::vector<int64_t> wino4_emu_weight_shape(int64_t out_channels, int64_t red_channels) {
+  return {wino4_emu_pad_reduction(red_channels) / 16, wino4_pad_output(out_channels) / 64, 36,
+          1024};
+}
+
+at::Tensor wino4_weight_emu(const at::Tensor& w, bool flip,
+                            const c10::optional<at::Tensor>& out) {
+  check_f32_gpu(w, "weight");
+  TORCH_CHECK(w.dim() == 4 && w.size(2) == 3 && w.size(3) == 3, "weight must be [K][C][3][3]");
+  const int64_t out_channels = flip ? w.size(1) : w.size(0);
+  const int64_t red_channels = flip ? w.size(0) : w.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  const auto wc = w.contiguous();
+  auto u = transform_out(out, wino4_emu_weight_shape(out_channels, red_channels), w);
+  TORCH_CHECK(u.is_contiguous(), "out must be contiguous");
+  if (u.numel() == 0) return u;
+  launch_wino4_emu_weight(wc.data_ptr<float>(), u.data_ptr<float>(), out_channels, red_channels,
+                          flip, stream_of(w));
+  return u;
+}
+
 at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
                       const c10::optional<at::Tensor>& bias, int64_t out_channels,
                       int64_t variant, int64_t splits) {
@@ -205,10 +228,18 @@ at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
   check_f32_gpu(u, "u");
   TORCH_CHECK(x.dim() == 4, "x must be NCHW");
   const int64_t n = x.size(0), r = x.size(1), h = x.size(2), w = x.size(3);
-  // the kernel's 36-float weight rows, channel padding and index ranges
-  TORCH_CHECK(u.dim() == 3 && u.size(2) == 36 && u.size(0) == wino4_pad_reduction(r) &&
-                  u.size(1) == wino4_pad_output(out_channels),
-              "F(4x4) transformed weight does not match the input/output channels");
+  if (wino4_variant_emu(static_cast<int>(variant))) {
+    // the split-bf16 kernel reads its own image (wino4_weight_emu)
+    TORCH_CHECK(u.is_contiguous() && u.sizes() == at::IntArrayRef(wino4_emu_weight_shape(
+                                                      out_channels, r)),
+                "variant ", variant, " needs the wino4_weight_emu image of these input/output "
+                "channels");
+  } else {
+    // the kernel's 36-float weight rows, channel padding and index ranges
+    TORCH_CHECK(u.dim() == 3 && u.size(2) == 36 && u.size(0) == wino4_pad_reduction(r) &&
+                    u.size(1) == wino4_pad_output(out_channels),
+                "F(4x4) transformed weight does not match the input/output channels");
+  }
   TORCH_CHECK(u.device() == x.device(), "u must live on the input's device");
   TORCH_CHECK(wino4_supported(n, r, h, w, out_channels),
               "input too large for the F(4x4) kernel (needs < 1 GiB); use wino_conv");
@@ -222,7 +253,7 @@ at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
   auto y = at::empty({n, out_channels, h, w}, x.options());
   if (y.numel() == 0) return y;
   TORCH_CHECK(variant == -1 || wino4_variant_known(static_cast<int>(variant)),
-              "variant must be -1, 4-10, 12, 14-18 or 20-22");
+              "variant must be -1, 4-10, 12, 14-18, 20-22 or 24");
   const WinoPlan plan = wino4_plan(n, r, h, w, out_channels, static_cast<int>(variant),
                                    static_cast<int>(splits));
   at::Tensor ws;
@@ -443,6 +474,7 @@ TORCH_LIBRARY(tgpipe, m) {
   m.def("wino_conv(Tensor x, Tensor u, Tensor? bias, int out_channels, int variant=-1, "
         "int splits=0) -> Tensor");
   m.def("wino4_weight(Tensor w, bool flip, Tensor? out=None) -> Tensor");
+  m.def("wino4_weight_emu(Tensor w, bool flip, Tensor? out=None) -> Tensor");
   m.def("wino4_wgrad(Tensor x, Tensor dy, int splits=0, int variant=0, Tensor? into=None) -> Tensor");
   m.def("wino4_conv(Tensor x, Tensor u, Tensor? bias, int out_channels, int variant=-1, "
         "int splits=0) -> Tensor");
@@ -472,6 +504,7 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("wino_conv", &tgpipe::wino_conv);
   m.impl("wino_wgrad", &tgpipe::wino_wgrad);
   m.impl("wino4_weight", &tgpipe::wino4_weight);
+  m.impl("wino4_weight_emu", &tgpipe::wino4_weight_emu);
   m.impl("wino4_conv", &tgpipe::wino4_conv);
   m.impl("wino4_wgrad", &tgpipe::wino4_wgrad);
   m.impl("bg_weight", &tgpipe::bg_weight);

@@ -73,7 +73,7 @@ void launch_wino_conv(const float* x, const float* u, const float* bias, float* 
 
 // Winograd F(4x4,3x3) (winograd_f4.hip): same convolution, 36 MFMA multiplies per 16
 // output pixels.  Transformed weights U4[Rp4/4][Op4/16][4][16][36] (Rp4 = multiple of 4,
-// Op4 = multiple of 64).  The variants (4-10, 12, 14-18, 20-22) are the rows of
+// Op4 = multiple of 64).  The variants (4-10, 12, 14-18, 20-22, 24) are the rows of
 // winograd_f4.hip's kF4Variants, described in that file's header comment.  wino4_plan
 // resolves the id that runs (an unknown id or -1: 5; a row-staged variant whose width
 // precondition fails: its fallback), the split-K count and the workspace, which for the
@@ -85,6 +85,14 @@ bool wino4_supported(int64_t n, int64_t r, int64_t h, int64_t w, int64_t o);
 void launch_wino4_weight(const float* w, float* u, int64_t out_channels, int64_t red_channels,
                          bool flip, hipStream_t stream);
 bool wino4_variant_known(int variant);
+// Variant 24 (the fused kernel on the bf16 matrix pipes, precision levels high / medium)
+// takes its own weight image: bf16 hi and mid planes of U, the reduction padded to 16
+// channels, wino4_emu_weight_numel floats' worth (winograd_f4.hip has the order).
+bool wino4_variant_emu(int variant);
+int64_t wino4_emu_pad_reduction(int64_t r);
+int64_t wino4_emu_weight_numel(int64_t out_channels, int64_t red_channels);
+void launch_wino4_emu_weight(const float* w, float* u, int64_t out_channels,
+                             int64_t red_channels, bool flip, hipStream_t stream);
 WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                     int variant, int splits);
 void launch_wino4_conv(const float* x, const float* u, const float* bias, float* y, float* ws,

@@ -38,6 +38,10 @@
 //   18       6 with the weight slab two steps ahead in a three-image LDS ring
 //            (f4_conv_ring_kernel; TGPIPE_F4_FUSED_VARIANT=18)
 //   20-22    timing ablations of 16 (wrong results; W % 4 == 0 and W >= 24, else run as 6)
+//   24       fused, on the bf16 matrix pipes: the three `high` partial products of split-bf16
+//            U and V (f4_conv_emu_kernel; its own weight image, launch_wino4_emu_weight;
+//            16-channel chunks)        <- conv precision high / medium, 64-256 output channels
+//            (23 is not an id: the recorded plans pin it as unknown)
 // Weight-gradient variants (wino4_wgrad_plan):
 //    0       fused, f4_wgrad_kernel
 //    1       non-fused: f4_wg_vx / f4_wg_mdy transform passes, then f4_wgrad_gemm_kernel
@@ -2270,6 +2274,200 @@ __global__ __launch_bounds__(256, 2) void bg_gemm_emu_kernel(
   }
 }
 
+// ---- fused F(4x4) on the bf16 matrix pipes (variant 24; precision levels high / medium) ----
+// f4_conv_kernel's workgroup (8 waves, 64 output channels x 32 tiles, wave (wo, wt) owns 16
+// channels x 16 tiles at all 36 positions, output transform in registers) with the
+// Winograd-domain products as the three `high` partial products of split-bf16 operands,
+// hi.hi + hi.mid + mid.hi (bg_split3's hi and mid; bg_gemm_emu_kernel<.., true> has the
+// reasons).  One pipeline chunk = 16 reduction channels:
+//   1. all eight waves load one 6x6 patch each (tile 16*(wave & 1) + (lane & 15), channel
+//      4*(wave >> 1) + (lane >> 4) of the chunk), transform it, split it and write the V
+//      image of the chunk: 36 positions x 2 tile groups x 1 KiB = 72 KiB, written once;
+//   2. the 36 positions are walked in six groups of six; a group's U slice (24 KiB) comes
+//      by LDS-DMA into a two-slot ring, one group ahead, so the image of a chunk never
+//      stands in LDS whole (64 x 16 x 36 x 2 planes x 2 B = 144 KiB would not fit).
+// Per position and wave two MFMAs: a v_mfma_f32_16x16x32_bf16 whose K axis carries the 16
+// channels twice, A = [U_hi | U_hi], B = [V_hi | V_mid] (hi.hi + hi.mid), and a
+// v_mfma_f32_16x16x16_bf16 of U_mid and V_hi.  A and B fragments of one MFMA take their k
+// from the same (lane group, element), so the products pair up by construction.
+//
+// LDS block of (position, 16 rows), 1 KiB, rows = output channels (U) or tiles (V):
+//   [plane hi, mid][half h][16 rows][8 channels 8h .. 8h+7] bf16
+// The 16x16x32 B fragment of lane l is the 16 bytes at 16*l (lane group g = 2*plane + h);
+// its A fragment is the hi plane's 16 bytes of (h = g & 1, row): lane groups g and g + 2
+// read the same address.  The 16x16x16 fragments (channels 4g .. 4g+3) are 8 bytes at
+// (h = g >> 1, row) + 8*(g & 1), of U's mid plane and of V's hi plane.  Every wave read
+// covers whole 256- or 512-byte runs: conflict-free.
+//
+// U image in HBM: [Rp/16 chunks][Op/64][36 positions][4 channel groups][1 KiB block], so
+// the slice of (chunk, channel block, position group) is 24 contiguous KiB.
+constexpr int kEC = 16;                      // reduction channels per chunk
+constexpr int kEPG = 6;                      // positions per U slice
+constexpr int kEBlock = 1024;                // bytes of one (position, 16 rows) block
+constexpr int kEUSlice = kEPG * 4 * kEBlock;  // 24 KiB
+constexpr int kEVImg = kP * 2 * kEBlock;     // 72 KiB
+typedef short shortx4 __attribute__((ext_vector_type(4)));
+
+// hi / mid planes of U = G g G^T in the order above; zeros in the channel padding.
+__global__ __launch_bounds__(256) void f4_weight_emu_kernel(const float* __restrict__ w,
+                                                           float* __restrict__ u, int O, int R,
+                                                           int Op, int Rp, bool flip) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (idx >= static_cast<int64_t>(Rp) * Op) return;
+  const int r = static_cast<int>(idx / Op);
+  const int o = static_cast<int>(idx % Op);
+  float v[kP];
+  f4_weight_tile(w, O, R, o, r, flip, v);
+  const int c = r % kEC;
+  char* dst = reinterpret_cast<char*>(u) +
+              ((static_cast<int64_t>(r / kEC) * (Op / 64) + o / 64) * kP * 4 + (o % 64) / 16) *
+                  kEBlock +
+              (((c >> 3) * 16 + o % 16) * 8 + (c & 7)) * 2;
+#pragma unroll
+  for (int b = 0; b < kP; ++b) {
+    const __bf16 h = static_cast<__bf16>(v[b]);
+    const __bf16 m = static_cast<__bf16>(v[b] - static_cast<float>(h));
+    *reinterpret_cast<__bf16*>(dst + b * 4 * kEBlock) = h;
+    *reinterpret_cast<__bf16*>(dst + b * 4 * kEBlock + 512) = m;
+  }
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(512, 1) void f4_conv_emu_kernel(
+    const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ bias,
+    float* __restrict__ y, int R, int H, int W, int O, int Rp, int Op, int TH, int TW, int P,
+    int tblocks, int oblocks, int splits, uint32_t x_bytes) {
+  __shared__ __attribute__((aligned(16))) char lds[kEVImg + 2 * kEUSlice];  // 120 KiB
+  char* const vimg = lds;
+  char* const uring = lds + kEVImg;
+
+  // XCD-aware bijective remap, as f4_conv_kernel
+  const int nwg = tblocks * oblocks * splits;
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7;
+  const int qq = nwg >> 3, rr = nwg & 7;
+  const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
+  const int ob = wgid % oblocks;
+  const int tb = (wgid / oblocks) % tblocks;
+  const int z = wgid / (oblocks * tblocks);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wo = wave & 3;
+  const int wt = wave >> 2;
+  const int t0 = tb * kT;
+  const int o0 = ob * 64;
+  const int HW = H * W;
+  const int tpi = TH * TW;
+
+  const int nchunks = Rp / kEC;
+  const int c_begin = z * nchunks / splits;
+  const int c_end = (z + 1) * nchunks / splits;
+  floatx4 acc[kP];
+#pragma unroll
+  for (int i = 0; i < kP; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  // this thread's patch of every chunk, and where its 72 bf16 values go in the V image
+  const int pt = (wave & 1) * 16 + (lane & 15);
+  const int pc = (wave >> 1) * 4 + (lane >> 4);
+  const __amdgpu_buffer_rsrc_t xr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), static_cast<short>(0),
+                                        static_cast<int>(x_bytes), 0x00020000);
+  F4Patch p;
+  f4_fwd_offsets(p, t0 + pt, pc, P, tpi, TW, R, H, W);
+  char* const vmine =
+      vimg + (pt >> 4) * kEBlock + (((pc >> 3) * 16 + (pt & 15)) * 8 + (pc & 7)) * 2;
+  const uint32_t chunk_bytes = static_cast<uint32_t>(kEC) * HW * 4;
+
+  // fragment addresses within a block (lane group g, row = lane & 15)
+  const int g = lane >> 4, row = lane & 15;
+  const int a32 = wo * kEBlock + ((g & 1) * 16 + row) * 16;
+  const int a16 = wo * kEBlock + 512 + ((g >> 1) * 16 + row) * 16 + (g & 1) * 8;
+  const int b32 = wt * kEBlock + lane * 16;
+  const int b16 = wt * kEBlock + ((g >> 1) * 16 + row) * 16 + (g & 1) * 8;
+
+  // slice (chunk, position group) of this channel block: 24 pieces of 1 KiB, 3 per wave
+  const char* const ubase = reinterpret_cast<const char*>(u);
+  const int64_t ochunk = static_cast<int64_t>(Op / 64);
+  auto issue_slice = [&](int chunk, int pg, int slot) {
+    const char* src = ubase + ((static_cast<int64_t>(chunk) * ochunk + ob) * kP + pg * kEPG) * 4 *
+                                  kEBlock;
+    char* dst = uring + slot * kEUSlice;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int piece = i * 8 + wave;
+      __builtin_amdgcn_global_load_lds((glob_void_t*)(src + piece * 1024 + lane * 16),
+                                       (lds_void_t*)(dst + piece * 1024), 16, 0, 0);
+    }
+  };
+
+  if (c_begin < c_end) issue_slice(c_begin, 0, 0);
+  for (int ck = c_begin; ck < c_end; ++ck) {
+    // -- V image of the chunk: B^T d B, split, one 2-byte store per (position, plane) ------
+    f4_load_patch<kVec>(p, xr, ck * chunk_bytes);
+    if (ck * kEC + pc >= R) {  // channel padding: the next image's data, or out of range
+#pragma unroll
+      for (int b = 0; b < kP; ++b) p.d[b] = 0.f;
+    }
+    f4_transform(p);
+#pragma unroll
+    for (int b = 0; b < kP; ++b) {
+      const __bf16 h = static_cast<__bf16>(p.d[b]);
+      const __bf16 m = static_cast<__bf16>(p.d[b] - static_cast<float>(h));
+      *reinterpret_cast<__bf16*>(vmine + b * 2 * kEBlock) = h;
+      *reinterpret_cast<__bf16*>(vmine + b * 2 * kEBlock + 512) = m;
+    }
+    __syncthreads();  // V written; the first slice's LDS-DMA drained (vmcnt 0)
+#pragma unroll
+    for (int pg = 0; pg < kP / kEPG; ++pg) {
+      const int slot = pg & 1;
+      if (pg + 1 < kP / kEPG) {
+        issue_slice(ck, pg + 1, slot ^ 1);
+      } else if (ck + 1 < c_end) {
+        issue_slice(ck + 1, 0, slot ^ 1);
+      }
+      const char* us = uring + slot * kEUSlice;
+#pragma unroll
+      for (int hq = 0; hq < kEPG; hq += 3) {
+        bf16x8 fa[3], fb[3];
+        shortx4 ga[3], gb[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int pos = pg * kEPG + hq + q;
+          fa[q] = *reinterpret_cast<const bf16x8*>(us + (hq + q) * 4 * kEBlock + a32);
+          fb[q] = *reinterpret_cast<const bf16x8*>(vimg + pos * 2 * kEBlock + b32);
+          ga[q] = *reinterpret_cast<const shortx4*>(us + (hq + q) * 4 * kEBlock + a16);
+          gb[q] = *reinterpret_cast<const shortx4*>(vimg + pos * 2 * kEBlock + b16);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int pos = pg * kEPG + hq + q;
+          acc[pos] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[q], fb[q], acc[pos], 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int pos = pg * kEPG + hq + q;
+          acc[pos] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ga[q], gb[q], acc[pos], 0, 0, 0);
+        }
+      }
+      // The group's MFMAs stay ahead of the barrier: left to the scheduler, the last ones
+      // sink below it, next to the address arithmetic of the following LDS-DMA, which
+      // reuses their operand registers.
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();  // the slot and (after the last group) the V image are free again
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // -- output transform, as f4_conv_kernel ------------------------------------------------
+  const int tp = t0 + wt * 16 + (lane & 15);
+  if (tp >= P) return;
+  float* ydst = y + static_cast<int64_t>(z) * (P / tpi) * O * HW;
+  f4_output_transform(acc, ydst, bias != nullptr && splits == 1 ? bias : nullptr, tp, tpi, TW,
+                      H, W, O, o0 + wo * 16 + 4 * (lane >> 4));
+}
+
 // Y = A^T (sum_z M[z]) A (+ bias): one thread per (output channel, tile), consecutive
 // threads on consecutive tiles (coalesced reads of each position's M row).
 __global__ __launch_bounds__(256) void bg_output_f4_kernel(
@@ -2814,6 +3012,8 @@ struct F4Variant {
   F4ConvKernel narrow;   // taken instead below 6 tiles per row, if any
   int min_w;             // > 0: needs W % 4 == 0 and W >= min_w, ...
   int fallback;          // ... and runs as this id otherwise
+  int chunk = kC;        // reduction channels per pipeline step: the padding of R, and the
+                         // unit split-K divides.  16: the split-bf16 kernel and its U image
 };
 // 16-byte centre loads pay off in the 4-wave variants only: the 8-wave one ran 4-16 % slower
 // with them (12 against 6; benchmarks/wino_variants.py, profiles/wino_f4_variants.json), so
@@ -2837,7 +3037,15 @@ constexpr F4Variant kF4Variants[] = {
     {20, 4, f4_conv_rows_kernel<46, 3, 4, 8>, nullptr, nullptr, 24, 6},
     {21, 4, f4_conv_rows_kernel<46, 3, 4, 1>, nullptr, nullptr, 24, 6},
     {22, 4, f4_conv_rows_kernel<46, 3, 4, 7>, nullptr, nullptr, 24, 6},
+    {24, 4, f4_conv_emu_kernel<false>, f4_conv_emu_kernel<true>, nullptr, 0, 0, kEC},
 };
+// Modelled time of one 16-channel chunk of a variant-24 workgroup for split_k_by_cost,
+// fitted to benchmarks/split_sweep.py --ops emu (profiles/r11/f4_emu/split_sweep_emu.json):
+// one-round grids take ~31 us at 4 chunks, ~50 us at 8 and 186 us at 32, i.e. ~5.2 us per
+// chunk over ~11 us of launch, prologue and output transform.  With the reduce-pass terms
+// of the exact kernels the model then picks the measured best count, or one within 1 %
+// of it, on the swept ResNet / U-Net shapes.
+constexpr double kEmuStepUs = 5.2;
 const F4Variant* f4_variant(int id) {
   for (const F4Variant& v : kF4Variants)
     if (v.id == id) return &v;
@@ -2846,6 +3054,29 @@ const F4Variant* f4_variant(int id) {
 }  // namespace
 
 bool wino4_variant_known(int variant) { return f4_variant(variant) != nullptr; }
+
+bool wino4_variant_emu(int variant) {
+  const F4Variant* v = f4_variant(variant);
+  return v != nullptr && v->chunk == kEC;
+}
+
+int64_t wino4_emu_pad_reduction(int64_t r) { return (r + kEC - 1) / kEC * kEC; }
+
+int64_t wino4_emu_weight_numel(int64_t out_channels, int64_t red_channels) {
+  // two bf16 planes of 36 values per padded channel pair, counted in floats
+  return wino4_emu_pad_reduction(red_channels) * wino4_pad_output(out_channels) * kP;
+}
+
+void launch_wino4_emu_weight(const float* w, float* u, int64_t out_channels,
+                             int64_t red_channels, bool flip, hipStream_t stream) {
+  const int64_t Op = wino4_pad_output(out_channels);
+  const int64_t Rp = wino4_emu_pad_reduction(red_channels);
+  const int64_t total = Rp * Op;
+  hipLaunchKernelGGL(f4_weight_emu_kernel, dim3(static_cast<unsigned>((total + 255) / 256)),
+                     dim3(256), 0, stream, w, u, static_cast<int>(out_channels),
+                     static_cast<int>(red_channels), static_cast<int>(Op), static_cast<int>(Rp),
+                     flip);
+}
 
 WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                     int variant, int splits) {
@@ -2857,7 +3088,7 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
   const int og = plan.og = v->og;
   const int64_t P = n * ((h + 3) / 4) * ((w + 3) / 4);
   const int64_t blocks = ((P + kT - 1) / kT) * ((out_channels + 16 * og - 1) / (16 * og));
-  const int64_t steps = wino4_pad_reduction(red_channels) / kC;
+  const int64_t steps = (red_channels + v->chunk - 1) / v->chunk;
   if (splits > 0) {
     plan.splits = static_cast<int>(std::min<int64_t>(splits, steps));
   } else {
@@ -2866,9 +3097,11 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
     // 32-channel workgroups ~1.9 us, two per CU), and per extra split ~0.23 us per MB of
     // output partials plus ~11.6 us for the reduce pass.  (The old ">= 16 steps per split"
     // rule kept ResNet's 28^2 x 128 layers at 22 images on 2 splits: 49 -> 41 us at 3.)
+    // The split-bf16 kernel's 16-channel chunk: kEmuStepUs (see there).
     const double mb = static_cast<double>(n) * out_channels * h * w * 4 / 1e6;
-    plan.splits = static_cast<int>(split_k_by_cost(blocks, steps, og == 4 ? 256 : 512,
-                                                   og == 4 ? 2.1 : 1.9, 11.6, 0.23, mb, 64));
+    const double step_us = v->chunk == kEC ? kEmuStepUs : og == 4 ? 2.1 : 1.9;
+    plan.splits = static_cast<int>(
+        split_k_by_cost(blocks, steps, og == 4 ? 256 : 512, step_us, 11.6, 0.23, mb, 64));
   }
   plan.workspace = plan.splits > 1 ? plan.splits * n * out_channels * h * w : 0;
   if (v->kernel == nullptr) {  // + the transformed input V4[P/32][Rp/4][4][32][36], first
@@ -2880,11 +3113,11 @@ WinoPlan wino4_plan(int64_t n, int64_t red_channels, int64_t h, int64_t w, int64
 void launch_wino4_conv(const float* x, const float* u, const float* bias, float* y, float* ws,
                        int64_t n, int64_t red_channels, int64_t h, int64_t w, int64_t out_channels,
                        const WinoPlan& plan, hipStream_t stream) {
-  const int64_t Rp = wino4_pad_reduction(red_channels);
+  const F4Variant& v = *f4_variant(plan.variant);  // wino4_plan's: a row of the table
+  const int64_t Rp = (red_channels + v.chunk - 1) / v.chunk * v.chunk;
   const int64_t Op = wino4_pad_output(out_channels);
   const int64_t th = (h + 3) / 4, tw = (w + 3) / 4;
   const int64_t P = n * th * tw;
-  const F4Variant& v = *f4_variant(plan.variant);  // wino4_plan's: a row of the table
   const int og = v.og;
   const int tblocks = static_cast<int>((P + kT - 1) / kT);
   const int oblocks = static_cast<int>((out_channels + 16 * og - 1) / (16 * og));

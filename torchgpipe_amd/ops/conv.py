@@ -46,7 +46,7 @@ import torch
 from torch import Tensor, nn
 import torch.nn.functional as F
 
-from torchgpipe_amd.ops import _ext, gradacc
+from torchgpipe_amd.ops import _ext, gradacc, precision
 
 __all__ = ['WinogradConv2d', 'winograd_conv2d', 'wino_eligible', 'new_step',
            'clear_winograd_caches', 'cache_bytes', 'refresh_step_caches', 'hold_cache',
@@ -158,6 +158,8 @@ def _derive(weight: Tensor, slot: Tuple, out: Optional[Tensor] = None) -> Tensor
         w = w.contiguous()
         if bg:
             return ops.bg_weight(w, flip, bg, out)
+        if f4 == 'emu':
+            return ops.wino4_weight_emu(w, flip, out)
         return ops.wino4_weight(w, flip, out) if f4 else ops.wino_weight(w, flip, out)
 
 
@@ -184,8 +186,9 @@ class _TransformCache:
     """Derived weights keyed by (storage, version, device, step) of the parameter.
 
     Entries per slot ``(flip, f4, bg)``: F(2x2) ``U[Rp][Op][16]``, F(4x4)
-    ``U4[Rp/4][Op/16][4][16][36]``, the batched-GEMM layouts, or the transpose (slot
-    ``(True, True, 'T')``).  Each entry is ``(key, tensor, ready event)``.
+    ``U4[Rp/4][Op/16][4][16][36]``, its split-bf16 image (``f4 = 'emu'``), the batched-GEMM
+    layouts, or the transpose (slot ``(True, True, 'T')``).  Each entry is ``(key, tensor,
+    ready event)``.
     """
 
     __slots__ = ('_entries', '_weight', '__weakref__')
@@ -229,11 +232,13 @@ class _TransformCache:
                 _CACHE_BYTES[dev] = _CACHE_BYTES.get(dev, 0) + size
             return u
 
-    def get(self, weight: Tensor, flip: bool, f4: bool = False, bg: int = 0) -> Tensor:
+    def get(self, weight: Tensor, flip: bool, f4: bool = False, bg: int = 0,
+            emu: bool = False) -> Tensor:
         """The transformed weight for ``flip`` (backward-data) and the kernel family:
-        F(2x2) (default), F(4x4) fused (``f4``) or the batched-GEMM layout of F(4x4) /
+        F(2x2) (default), F(4x4) fused (``f4``; with ``emu`` the bf16 hi / mid planes of
+        the fused split-bf16 kernel, variant 24) or the batched-GEMM layout of F(4x4) /
         F(2x2) (``bg`` = 4 / 2)."""
-        return self._lookup(weight, (flip, f4, bg))
+        return self._lookup(weight, (flip, 'emu' if f4 and emu else f4, bg))
 
     def get_transposed(self, weight: Tensor) -> Tensor:
         """``weight`` as ``[ci][co][kh][kw]`` (contiguous): the backward-data GEMM operand
@@ -407,6 +412,55 @@ def _bg_kind(x: Tensor, out_channels: int) -> int:
     return kind
 
 
+# The fused F(4x4) kernel on the bf16 matrix pipes (f4_conv_emu_kernel: the three `high`
+# partial products of split-bf16 U and V), which the precision levels 'high' and 'medium'
+# may route the < 512-channel layers to.
+F4_EMU_VARIANT = 24
+
+
+def f4_emu_faster(shape: Sequence[int], out_channels: int) -> bool:
+    """Whether variant 24 measured faster than the exact fused kernel picked for this
+    (input shape, output channels): benchmarks/f4_emu_bench.py, profiles/r11/f4_emu.  It
+    won by 9-38 %, beyond the spread of the exact kernel's repetitions, on every measured
+    shape with 64-256 output channels, 32-512 input channels and planes of 24^2 - 192^2
+    (U-Net(5,64) at 40 images, ResNet's 64 / 128-channel 3x3s at 22 and 110), and lost
+    22-24 % at 32 output channels, where the exact kernel runs 32-channel workgroups and
+    this one exists for 64 only.  Shapes outside the measured classes stay exact."""
+    _, r, h, w = shape
+    return 64 <= out_channels < 512 and r >= 32 and min(h, w) >= 24
+
+
+def f4_variant(shape: Sequence[int], out_channels: int, level: Optional[str] = None) -> int:
+    """The F(4x4) forward / backward-data variant (a row of ``kF4Variants``) for an input of
+    ``shape`` (N, R, H, W) and ``out_channels``, at the conv precision ``level`` (default:
+    the level in force now).  A pure function of its arguments and that level."""
+    # 32-channel workgroups (variant 7) when a 64-channel one (variant 6) would idle half its
+    # waves, or when the 64-channel grid covers well under one workgroup per CU (before
+    # split-K): profiles/wino_f4_variants.json, 16 images at 12^2 / 24^2 (80 / 144 blocks)
+    # 12 % / 10 % faster on 32 channels; 40 images at 12^2 (192 blocks) and every larger grid
+    # 3-14 % faster on 64.  Both copy the weight slab with LDS-DMA (variants 4 / 5 stage it
+    # through registers: 2-12 % slower).  From 512 output channels the input transform runs
+    # as its own pass (variants 14 / 15: V written once, then a GEMM kernel with both
+    # operands by LDS-DMA): 20-28 % faster at 512-2048 channels, where V is re-read by >= 8
+    # channel blocks; slower on the wide planes with few channels (64 @ 192^2: 0.75 vs
+    # 0.52 ms).
+    if level is None:
+        level = precision.get_conv_precision()
+    n, _, h, w = shape
+    tiles = n * ((h + 3) // 4) * ((w + 3) // 4)
+    blocks = -(-tiles // 32) * -(-out_channels // 64)
+    if out_channels >= 512:
+        # 6x6 planes: the 32-channel GEMM (0.67 vs 0.73 ms at 40 images)
+        small = blocks < 160 or min(h, w) < F4_MIN_PLANE
+        return 15 if small else 14
+    variant = 7 if out_channels <= 32 or blocks < 160 else _F4_FUSED_VARIANT
+    if variant == 16 and w < F4_ROWS_MIN_WIDTH:
+        variant = 6
+    if level != 'highest' and f4_emu_faster(shape, out_channels):
+        variant = F4_EMU_VARIANT
+    return variant
+
+
 def _conv(x: Tensor, cache: _TransformCache, weight: Tensor, bias: Optional[Tensor],
           flip: bool) -> Tensor:
     """One Winograd convolution launch: forward (flip=False) or backward-data (flip=True)."""
@@ -426,17 +480,9 @@ def _conv(x: Tensor, cache: _TransformCache, weight: Tensor, bias: Optional[Tens
         # 15: V written once, then a GEMM kernel with both operands by LDS-DMA): 20-28 %
         # faster at 512-2048 channels, where V is re-read by >= 8 channel blocks; slower
         # on the wide planes with few channels (64 @ 192^2: 0.75 vs 0.52 ms).
-        tiles = x.shape[0] * ((x.shape[2] + 3) // 4) * ((x.shape[3] + 3) // 4)
-        blocks = -(-tiles // 32) * -(-out_channels // 64)
-        if out_channels >= 512:
-            # 6x6 planes: the 32-channel GEMM (0.67 vs 0.73 ms at 40 images)
-            small = blocks < 160 or min(x.shape[2], x.shape[3]) < F4_MIN_PLANE
-            variant = 15 if small else 14
-        else:
-            variant = 7 if out_channels <= 32 or blocks < 160 else _F4_FUSED_VARIANT
-            if variant == 16 and x.shape[3] < F4_ROWS_MIN_WIDTH:
-                variant = 6
-        return ops.wino4_conv(x, cache.get(weight, flip, True), bias, out_channels, variant)
+        variant = f4_variant(x.shape, out_channels)
+        u = cache.get(weight, flip, True, emu=variant == F4_EMU_VARIANT)
+        return ops.wino4_conv(x, u, bias, out_channels, variant)
     return ops.wino_conv(x, cache.get(weight, flip), bias, out_channels)
 
 

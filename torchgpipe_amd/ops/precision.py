@@ -3,8 +3,10 @@
 The implicit-GEMM tile configurations 7-11 (``csrc/conv_gemm.hip``) and the batched-GEMM
 Winograd kernel (``bg_gemm_emu_kernel``, ``csrc/winograd_f4.hip``) emulate an fp32 product
 on the bf16 matrix pipes: each operand is split exactly into three bf16 parts
-``hi + mid + lo`` and a product is six partial products.  The levels are those of
-:func:`torch.set_float32_matmul_precision`:
+``hi + mid + lo`` and a product is six partial products.  At the reduced levels the fused
+F(4x4) Winograd forward / backward-data of the 64-256-channel 3x3 layers runs on them too
+(``f4_conv_emu_kernel``, the three ``'high'`` products; ``ops.conv.f4_variant`` routes).
+The levels are those of :func:`torch.set_float32_matmul_precision`:
 
 ``'highest'`` (default)
     all six partial products: fp32 error bounds.
@@ -13,14 +15,16 @@ on the bf16 matrix pipes: each operand is split exactly into three bf16 parts
     half the MFMA work, two thirds of the LDS fragment traffic.
 ``'medium'``
     ``hi*hi``: bf16 operands, fp32 accumulation; ``2**-8`` per product, one sixth of the
-    MFMA work.  The Winograd kernel runs ``'high'`` at this level (plain bf16 operands lose
-    too much in the transform domain).
+    MFMA work.  The Winograd kernels run ``'high'`` at this level (plain bf16 operands
+    lose too much in the transform domain).
 
 The level is process-wide and read when a kernel is launched: a captured graph keeps the
 level it was captured at.  Set it before building ``GPipe`` / ``PipelineStage`` and do not
 change it inside a step (checkpoint recomputation must see the forward's level).  The f32
-MFMA configurations 0-6, the fused Winograd kernels of the 64/128-channel layers and every
-library (MIOpen) path compute as before at every level; so do CPU tensors.  The level does
+MFMA configurations 0-6, the fused Winograd weight gradient of the 64/128-channel layers,
+the fused forward / backward-data kernels outside the routed shape classes
+(``ops.conv.f4_emu_faster``) and every library (MIOpen) path compute as before at every
+level; so do CPU tensors.  The level does
 not follow :func:`torch.get_float32_matmul_precision`.
 
 ``split_bf16`` and the ``reference_*`` functions are the fp64 oracle of these semantics.
