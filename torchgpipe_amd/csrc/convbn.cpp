@@ -1728,10 +1728,19 @@ at::Tensor avgpool3_backward(const at::Tensor& dy_in, int64_t h, int64_t w, int6
   return dx;
 }
 
-// U-Net decoder: cat(upsample2x(x), skip) and its backward for x (unet_ops.hip).
+// The kernels below read their inputs with 8- and 16-byte vector accesses.  A contiguous
+// tensor can still start anywhere (a view into a flat buffer): it is copied into a fresh
+// allocation, which is aligned.  Aligned tensors pass through untouched.
+at::Tensor aligned16(const at::Tensor& t) {
+  if ((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0) return t;
+  return t.clone(at::MemoryFormat::Contiguous);
+}
+
+// ResNet's residual join, then the U-Net decoder: cat(upsample2x(x), skip) and its backward
+// for x (unet_ops.hip).
 at::Tensor add_relu_forward(const at::Tensor& a_in, const at::Tensor& b_in) {
-  auto a = a_in.contiguous();
-  auto b = b_in.contiguous();
+  auto a = aligned16(a_in.contiguous());
+  auto b = aligned16(b_in.contiguous());
   check_f32(a, "a", a);
   check_f32(b, "b", a);
   TORCH_CHECK(a.sizes() == b.sizes(), "a and b must have one shape");
@@ -1743,8 +1752,8 @@ at::Tensor add_relu_forward(const at::Tensor& a_in, const at::Tensor& b_in) {
 }
 
 at::Tensor up2x_cat_forward(const at::Tensor& x_in, const at::Tensor& skip_in) {
-  auto x = x_in.contiguous();
-  auto skip = skip_in.contiguous();
+  auto x = aligned16(x_in.contiguous());
+  auto skip = aligned16(skip_in.contiguous());
   check_f32(x, "x", x);
   check_f32(skip, "skip", x);
   TORCH_CHECK(x.dim() == 4 && skip.dim() == 4 && skip.size(0) == x.size(0) &&
@@ -1767,7 +1776,8 @@ at::Tensor up2x_backward(const at::Tensor& dy_in, int64_t c) {
   auto dy = dy_in.narrow(1, 0, c);
   int64_t dy_img = image_stride_if_channel_slice(dy);
   if (dy_img == 0) {
-    dy = dy.contiguous();
+    // (not a dense, aligned channel slice: image_stride_if_channel_slice checks both)
+    dy = aligned16(dy.contiguous());
     dy_img = c * dy.size(2) * dy.size(3);
   }
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kFloat, "dy must be float32 on the GPU");

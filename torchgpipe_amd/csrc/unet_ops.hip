@@ -137,7 +137,10 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __rest
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // ResNet's residual join: y = relu(x + identity), one pass (the sum and the ReLU were two
-// ATen passes over the block output).
+// ATen passes over the block output).  A NaN sum stays NaN, as in ATen's relu (and in the
+// max pool above): a diverged branch must show at the join, not vanish into a 0.
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
+
 __global__ __launch_bounds__(256) void add_relu_kernel(const float* __restrict__ a,
                                                        const float* __restrict__ b,
                                                        float* __restrict__ y, int64_t quads,
@@ -148,15 +151,14 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const float* __restrict__
         reinterpret_cast<const floatx4*>(a)[q] + reinterpret_cast<const floatx4*>(b)[q];
     floatx4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = v[e] > 0.f ? v[e] : 0.f;
+    for (int e = 0; e < 4; ++e) o[e] = relu_nan(v[e]);
     reinterpret_cast<floatx4*>(y)[q] = o;
   }
   // tail (total % 4), by the first workgroup
   if (blockIdx.x == 0) {
     const int64_t i = quads * 4 + threadIdx.x;
     if (i < total) {
-      const float v = a[i] + b[i];
-      y[i] = v > 0.f ? v : 0.f;
+      y[i] = relu_nan(a[i] + b[i]);
     }
   }
 }
