@@ -9,10 +9,16 @@ which the U-Net's Philox dropout does not have).
     python benchmarks/unet_precision_speed.py --rounds 2 \\
         --out profiles/r11/f4_emu/unet_levels.json
 
+``--autocast`` adds a ``bf16-autocast`` run to every round: the same stage at 'highest'
+with every ``train_step`` under ``torch.autocast('cuda', dtype=torch.bfloat16)`` (library
+bf16 convolutions between the bf16 DropNormAct / pool / upsample kernels), with the same
+error report against the round's 'highest'.
+
 The level is set before the stage is built (checkpoint recomputation must see the forward's
 level), so every (round, level) builds its own stage from the same seed.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -31,8 +37,12 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
     return ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
 
 
+AUTOCAST = 'bf16-autocast'
+
+
 def run(level: str, batch: int, chunks: int, steps: int, warmup: int, ref: dict) -> dict:
-    precision.set_conv_precision(level)
+    amp = level == AUTOCAST
+    precision.set_conv_precision('highest' if amp else level)
     device = torch.device('cuda', 0)
     torch.manual_seed(0)
     model = unet(depth=5, num_convs=5, base_channels=64, input_channels=3, output_channels=1)
@@ -41,6 +51,13 @@ def run(level: str, batch: int, chunks: int, steps: int, warmup: int, ref: dict)
     x = torch.rand(batch, 3, 192, 192, device=device)
     target = torch.ones(batch, 1, 192, 192, device=device)
     loss = None
+    plain_step = stage.train_step
+
+    def train_step(*args):  # type: ignore[no-untyped-def]
+        with torch.autocast('cuda', dtype=torch.bfloat16) if amp else contextlib.nullcontext():
+            return plain_step(*args)
+
+    stage.train_step = train_step  # type: ignore[method-assign]
     for _ in range(warmup):
         loss = stage.train_step(x, target, F.binary_cross_entropy_with_logits)
     torch.cuda.synchronize()
@@ -81,6 +98,9 @@ def main() -> None:
     p.add_argument('--exact-fused', action='store_true',
                    help='keep the fused F(4x4) layers on the exact kernels at every level '
                         '(what the reduced levels did before variant 24)')
+    p.add_argument('--autocast', action='store_true',
+                   help="add a 'bf16-autocast' run (torch.autocast around every step, conv "
+                        "level 'highest') to every round")
     p.add_argument('--out', default=None)
     a = p.parse_args()
     if not _ext.available():
@@ -92,7 +112,7 @@ def main() -> None:
     try:
         for rnd in range(a.rounds):
             ref: dict = {}
-            for level in a.levels:
+            for level in list(a.levels) + ([AUTOCAST] if a.autocast else []):
                 row = dict(run(level, a.batch, a.chunks, a.steps, a.warmup, ref), round=rnd)
                 rows.append(row)
                 print(json.dumps(row), flush=True)

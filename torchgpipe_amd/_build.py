@@ -30,6 +30,7 @@ KERNEL_SOURCES = ['kernels.hip', 'winograd.hip', 'winograd_f4.hip', 'conv_gemm.h
                   'batchnorm.hip', 'pool.hip', 'unet_ops.hip']
 HOST_SOURCES = ['bindings.cpp', 'convbn.cpp']
 HEADERS = ['kernels.h', 'philox.h']
+HOST_HEADERS = ['aten_checks.h']  # ATen-side helpers: the host sources only
 
 
 def _torch_dirs() -> List[str]:
@@ -76,6 +77,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile (incrementally) and link ``_C.so``; returns its path."""
     os.makedirs(BUILD, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in HEADERS]
+    host_headers = [os.path.join(CSRC, h) for h in HOST_HEADERS]
     objects: List[str] = []
     relink = force or not os.path.exists(TARGET)
 
@@ -94,7 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src in HOST_SOURCES:
         path = os.path.join(CSRC, src)
         obj = os.path.join(BUILD, src + '.o')
-        if force or _stale(obj, [path] + headers):
+        if force or _stale(obj, [path] + headers + host_headers):
             _run(['g++', *common, '-DUSE_ROCM=1', '-DTORCH_API_INCLUDE_EXTENSION_H',
                   '-DTORCH_EXTENSION_NAME=_C', f'-D_GLIBCXX_USE_CXX11_ABI={_cxx11_abi()}',
                   f'-I{ROCM}/include', *torch_inc, f'-I{py_inc}', '-c', path, '-o', obj],

@@ -30,7 +30,7 @@ RNG replay (K4 in SURVEY §2.4).  Two mechanisms, both deterministic:
    autograd thread.
 """
 from collections import deque
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 import threading
 from typing import Any, Deque, Generator, Optional, Tuple, Union
 
@@ -40,6 +40,7 @@ from torch import Tensor
 from torchgpipe_amd.dependency import fork, join
 from torchgpipe_amd.microbatch import Batch
 from torchgpipe_amd.phony import get_phony
+from torchgpipe_amd.utils import autocast
 from torchgpipe_amd.utils.rng import RngTape
 
 __all__ = ['is_checkpointing', 'is_recomputing', 'checkpoint', 'Checkpointing']
@@ -124,7 +125,7 @@ class _Shared:
     """State shared by one Checkpoint/Recompute pair (the reference uses deques)."""
 
     __slots__ = ('function', 'input_atomic', 'recomputed', 'rng', 'tape', 'inputs',
-                 'versions')
+                 'versions', 'autocast')
 
     def __init__(self, function: Any, input_atomic: bool) -> None:
         self.function = function
@@ -142,6 +143,10 @@ class _Shared:
         self.recomputed: Deque[Recomputed] = deque(maxlen=1)
         self.rng: Deque[RNGSnapshot] = deque(maxlen=1)
         self.tape = RngTape()
+        # the autocast state of the checkpointed forward: the recomputation runs under it on
+        # whichever thread runs it, often after the user's autocast block has ended
+        # (torch.utils.checkpoint does the same)
+        self.autocast: Optional[autocast.AutocastState] = None
 
     def run_recompute(self, inputs: Tensors) -> None:
         if self.versions is not None and \
@@ -152,7 +157,8 @@ class _Shared:
                                f'{tuple(x._version for x in inputs)} now)')
         leaves = tuple(x.detach().requires_grad_(x.requires_grad) for x in inputs)
         snapshot = self.rng.pop()
-        with snapshot.restored(), self.tape.replaying():
+        amp = self.autocast.entered() if self.autocast is not None else nullcontext()
+        with snapshot.restored(), self.tape.replaying(), amp:
             with torch.enable_grad(), enable_recomputing():
                 output = self.function(leaves[0] if self.input_atomic else leaves)
         self.recomputed.append((output, leaves))
@@ -165,7 +171,14 @@ class Checkpoint(torch.autograd.Function):
         ctx.shared = shared
         shared.inputs = input
         shared.rng.append(RNGSnapshot(input[0].device))
-        with torch.no_grad(), enable_checkpointing(), shared.tape.recording():
+        shared.autocast = autocast.capture()
+        # (without autocast's weight-cast cache.  Where micro-batches share one autocast
+        # block -- PipelineStage on the calling thread; GPipe's worker tasks each enter and
+        # leave their own, which clears the cache -- a cast cached here, under no_grad,
+        # carries no graph, and except_last's last micro-batch, which runs with grad in the
+        # same block, would pick it up and lose its weight gradients)
+        with torch.no_grad(), enable_checkpointing(), shared.tape.recording(), \
+                shared.autocast.entered(cache=False):
             output = shared.function(input[0] if shared.input_atomic else input)
         # (after the function: its own in-place ops on its inputs are the recomputation's
         # business, as in the reference; what must not happen is a change in between)

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "aten_checks.h"
 #include "kernels.h"
 
 namespace tgpipe {
@@ -34,17 +35,25 @@ void check_f32_gpu(const at::Tensor& t, const char* name) {
 std::vector<at::Tensor> dna_forward(const at::Tensor& x, double p, double eps, double slope,
                                     int64_t seed, int64_t offset, bool dropout,
                                     const c10::optional<at::Tensor>& rng) {
-  check_f32_gpu(x, "x");
+  check_f32_or_bf16(x, "x", x);
   TORCH_CHECK(x.dim() >= 3, "expected (N, C, *spatial) input");
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must be in [0, 1)");
   const int64_t planes = x.size(0) * x.size(1);
   const int64_t s = planes == 0 ? 0 : x.numel() / planes;
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty_like(x);
-  auto opts = x.options();
+  auto opts = x.options().dtype(at::kFloat);  // the saved statistics stay fp32
   auto mean = at::empty({planes}, opts);
   auto rstd = at::empty({planes}, opts);
   auto scale = at::empty({planes}, opts);
+  if (x.scalar_type() == at::kBFloat16) {
+    launch_dna_forward(bf16_ptr(x), bf16_mut(y), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       scale.data_ptr<float>(), planes, s, static_cast<float>(p),
+                       static_cast<float>(eps), static_cast<float>(slope),
+                       static_cast<uint64_t>(seed), static_cast<uint64_t>(offset), dropout,
+                       rng_state(rng, x.device()), stream_of(x));
+    return {y, mean, rstd, scale};
+  }
   launch_dna_forward(x.data_ptr<float>(), y.data_ptr<float>(), mean.data_ptr<float>(),
                      rstd.data_ptr<float>(), scale.data_ptr<float>(), planes, s,
                      static_cast<float>(p), static_cast<float>(eps), static_cast<float>(slope),
@@ -55,9 +64,9 @@ std::vector<at::Tensor> dna_forward(const at::Tensor& x, double p, double eps, d
 
 at::Tensor dna_backward(const at::Tensor& dy_in, const at::Tensor& x, const at::Tensor& mean,
                         const at::Tensor& rstd, const at::Tensor& scale, double slope) {
-  check_f32_gpu(x, "x");
+  check_f32_or_bf16(x, "x", x);
   auto dy = dy_in.contiguous();
-  check_f32_gpu(dy, "dy");
+  check_f32_or_bf16(dy, "dy", x);
   TORCH_CHECK(dy.sizes() == x.sizes(), "dy and x must have the same shape");
   const int64_t planes = x.size(0) * x.size(1);
   const int64_t s = planes == 0 ? 0 : x.numel() / planes;
@@ -65,10 +74,25 @@ at::Tensor dna_backward(const at::Tensor& dy_in, const at::Tensor& x, const at::
               "saved statistics must have N*C elements");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto dx = at::empty_like(x);
+  if (x.scalar_type() == at::kBFloat16) {
+    launch_dna_backward(bf16_ptr(dy), bf16_ptr(x), mean.data_ptr<float>(),
+                        rstd.data_ptr<float>(), scale.data_ptr<float>(), bf16_mut(dx), planes, s,
+                        static_cast<float>(slope), stream_of(x));
+    return dx;
+  }
   launch_dna_backward(dy.data_ptr<float>(), x.data_ptr<float>(), mean.data_ptr<float>(),
                       rstd.data_ptr<float>(), scale.data_ptr<float>(), dx.data_ptr<float>(),
                       planes, s, static_cast<float>(slope), stream_of(x));
   return dx;
+}
+
+// The DropNormAct instance a plane of `s` elements of `elem_bytes` runs, its operands'
+// addresses off slot alignment by `misalign` bytes: (GROUP, V, form) -- host only.
+std::vector<int64_t> dna_plan_info(int64_t s, int64_t elem_bytes, int64_t misalign) {
+  TORCH_CHECK(elem_bytes == 4 || elem_bytes == 2, "elem_bytes must be 4 (fp32) or 2 (bf16)");
+  int64_t out[3];
+  dna_plan(s, static_cast<int>(elem_bytes), static_cast<uintptr_t>(misalign), out);
+  return {out[0], out[1], out[2]};
 }
 
 at::Tensor dropout(const at::Tensor& x_in, double p, int64_t seed, int64_t offset,
@@ -465,6 +489,8 @@ TORCH_LIBRARY(tgpipe, m) {
         "bool dropout, Tensor? rng=None) -> Tensor[]");
   m.def("dna_backward(Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor scale, "
         "float slope) -> Tensor");
+  // the DropNormAct instance for a plane size, element size and misalignment (host only)
+  m.def("dna_plan_info(int s, int elem_bytes, int misalign) -> int[]", &tgpipe::dna_plan_info);
   m.def("dropout(Tensor x, float p, int seed, int offset, Tensor? rng=None) -> Tensor");
   m.def("philox_uniform(int n, int seed, int offset, Device device, Tensor? rng=None) -> Tensor");
   m.def("spin(int ns, Device device) -> ()");

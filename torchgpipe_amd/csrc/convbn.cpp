@@ -18,6 +18,7 @@
 #include <tuple>
 #include <vector>
 
+#include "aten_checks.h"
 #include "kernels.h"
 
 namespace tgpipe {
@@ -543,8 +544,8 @@ void backward_data_into(const at::Tensor& wt, const at::Tensor& dz, const at::Te
 
 // A channel slice of a dense NCHW tensor (e.g. the gradient of one input of a
 // concatenation): dense within each image, any image stride.  Returns that stride, or 0.
-int64_t image_stride_if_channel_slice(const at::Tensor& t) {
-  if (t.dim() != 4 || t.scalar_type() != at::kFloat || !t.is_cuda()) return 0;
+int64_t image_stride_if_channel_slice(const at::Tensor& t, at::ScalarType dtype = at::kFloat) {
+  if (t.dim() != 4 || t.scalar_type() != dtype || !t.is_cuda()) return 0;
   const int64_t c = t.size(1), h = t.size(2), w = t.size(3);
   if (t.stride(3) != 1 || t.stride(2) != w || t.stride(1) != h * w) return 0;
   if (t.size(0) > 1 && t.stride(0) < c * h * w) return 0;
@@ -1754,15 +1755,21 @@ at::Tensor add_relu_forward(const at::Tensor& a_in, const at::Tensor& b_in) {
 at::Tensor up2x_cat_forward(const at::Tensor& x_in, const at::Tensor& skip_in) {
   auto x = aligned16(x_in.contiguous());
   auto skip = aligned16(skip_in.contiguous());
-  check_f32(x, "x", x);
-  check_f32(skip, "skip", x);
+  check_f32_or_bf16(x, "x", x, kMaxBytes / 4);
+  check_f32_or_bf16(skip, "skip", x, kMaxBytes / 4);
   TORCH_CHECK(x.dim() == 4 && skip.dim() == 4 && skip.size(0) == x.size(0) &&
                   skip.size(2) == 2 * x.size(2) && skip.size(3) == 2 * x.size(3),
               "skip must be [N][C2][2H][2W] for x [N][C1][H][W]");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto out = at::empty({x.size(0), x.size(1) + skip.size(1), skip.size(2), skip.size(3)},
                        x.options());
-  check_f32(out, "output", x);
+  check_f32_or_bf16(out, "output", x, kMaxBytes / 4);
+  if (x.scalar_type() == at::kBFloat16) {
+    launch_up2x_cat(bf16_ptr(x), bf16_ptr(skip), bf16_mut(out), x.size(0),
+                    static_cast<int>(x.size(1)), static_cast<int>(skip.size(1)),
+                    static_cast<int>(x.size(2)), static_cast<int>(x.size(3)), cur_stream(x));
+    return out;
+  }
   launch_up2x_cat(x.data_ptr<float>(), skip.data_ptr<float>(), out.data_ptr<float>(), x.size(0),
                   static_cast<int>(x.size(1)), static_cast<int>(skip.size(1)),
                   static_cast<int>(x.size(2)), static_cast<int>(x.size(3)), cur_stream(x));
@@ -1773,17 +1780,24 @@ at::Tensor up2x_cat_forward(const at::Tensor& x_in, const at::Tensor& skip_in) {
 at::Tensor up2x_backward(const at::Tensor& dy_in, int64_t c) {
   TORCH_CHECK(dy_in.dim() == 4 && dy_in.size(1) >= c && dy_in.size(2) % 2 == 0 &&
                   dy_in.size(3) % 2 == 0, "dy must be [N][>=C][2H][2W]");
+  const bool bf16 = dy_in.scalar_type() == at::kBFloat16;
   auto dy = dy_in.narrow(1, 0, c);
-  int64_t dy_img = image_stride_if_channel_slice(dy);
+  int64_t dy_img = image_stride_if_channel_slice(dy, bf16 ? at::kBFloat16 : at::kFloat);
   if (dy_img == 0) {
     // (not a dense, aligned channel slice: image_stride_if_channel_slice checks both)
     dy = aligned16(dy.contiguous());
     dy_img = c * dy.size(2) * dy.size(3);
   }
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kFloat, "dy must be float32 on the GPU");
+  TORCH_CHECK(dy.is_cuda() && (bf16 || dy.scalar_type() == at::kFloat),
+              "dy must be float32 or bfloat16 on the GPU");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
   const int64_t h = dy.size(2) / 2, w = dy.size(3) / 2;
   auto dx = at::empty({dy.size(0), c, h, w}, dy.options());
+  if (bf16) {
+    launch_up2x_backward(bf16_ptr(dy), bf16_mut(dx), dy.size(0), static_cast<int>(c),
+                         static_cast<int>(h), static_cast<int>(w), dy_img, cur_stream(dy));
+    return dx;
+  }
   launch_up2x_backward(dy.data_ptr<float>(), dx.data_ptr<float>(), dy.size(0),
                        static_cast<int>(c), static_cast<int>(h), static_cast<int>(w), dy_img,
                        cur_stream(dy));
@@ -1792,17 +1806,24 @@ at::Tensor up2x_backward(const at::Tensor& dy_in, int64_t c) {
 
 at::Tensor maxpool2x2_forward(const at::Tensor& x_in, const c10::optional<at::Tensor>& add) {
   auto x = x_in.contiguous();
-  check_f32(x, "x", x);
+  check_f32_or_bf16(x, "x", x, kMaxBytes / 4);
   TORCH_CHECK(x.dim() == 4, "x must be NCHW");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty({x.size(0), x.size(1), x.size(2) / 2, x.size(3) / 2}, x.options());
+  const bool bf16 = x.scalar_type() == at::kBFloat16;
   const float* ad = nullptr;
   at::Tensor add_c;
   if (add.has_value() && add->defined()) {
     add_c = add->contiguous();
-    check_f32(add_c, "add", x);
+    check_f32_or_bf16(add_c, "add", x, kMaxBytes / 4);
     TORCH_CHECK(add_c.sizes() == y.sizes(), "add must have the pooled shape");
-    ad = add_c.data_ptr<float>();
+    if (!bf16) ad = add_c.data_ptr<float>();
+  }
+  if (bf16) {
+    launch_maxpool2x2_forward(bf16_ptr(x), add_c.defined() ? bf16_ptr(add_c) : nullptr,
+                              bf16_mut(y), x.size(0) * x.size(1), static_cast<int>(x.size(2)),
+                              static_cast<int>(x.size(3)), cur_stream(x));
+    return y;
   }
   launch_maxpool2x2_forward(x.data_ptr<float>(), ad, y.data_ptr<float>(), x.size(0) * x.size(1),
                             static_cast<int>(x.size(2)), static_cast<int>(x.size(3)),
@@ -1812,20 +1833,27 @@ at::Tensor maxpool2x2_forward(const at::Tensor& x_in, const c10::optional<at::Te
 
 at::Tensor maxpool2x2_backward(const at::Tensor& x_in, const at::Tensor& dy_in) {
   auto x = x_in.contiguous();
-  check_f32(x, "x", x);
+  check_f32_or_bf16(x, "x", x, kMaxBytes / 4);
   TORCH_CHECK(x.dim() == 4 && dy_in.dim() == 4 && dy_in.size(2) == x.size(2) / 2 &&
                   dy_in.size(3) == x.size(3) / 2 && dy_in.size(1) == x.size(1) &&
                   dy_in.size(0) == x.size(0),
               "dy must be the pooled shape of x");
-  TORCH_CHECK(dy_in.scalar_type() == at::kFloat && dy_in.device() == x.device(),
-              "dy must be fp32 on x's device");
+  TORCH_CHECK(dy_in.scalar_type() == x.scalar_type() && dy_in.device() == x.device(),
+              "dy must have x's dtype on x's device");
   // a channel slice (gradient of one input of a concatenation) is read in place
-  const int64_t dy_img = image_stride_if_channel_slice(dy_in);
+  const int64_t dy_img = image_stride_if_channel_slice(dy_in, x.scalar_type());
   auto dy = dy_img > 0 ? dy_in : dy_in.contiguous();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   const bool odd = (x.size(2) & 1) || (x.size(3) & 1);
   auto dx = odd ? at::zeros_like(x) : at::empty_like(x);
   const int64_t c = x.size(1);
+  if (x.scalar_type() == at::kBFloat16) {
+    launch_maxpool2x2_backward(bf16_ptr(x), bf16_ptr(dy), bf16_mut(dx), x.size(0) * c,
+                               static_cast<int>(c), static_cast<int>(x.size(2)),
+                               static_cast<int>(x.size(3)),
+                               dy_img > 0 ? dy_img : c * dy.size(2) * dy.size(3), cur_stream(x));
+    return dx;
+  }
   launch_maxpool2x2_backward(x.data_ptr<float>(), dy.data_ptr<float>(), dx.data_ptr<float>(),
                              x.size(0) * c, static_cast<int>(c), static_cast<int>(x.size(2)),
                              static_cast<int>(x.size(3)),

@@ -25,6 +25,22 @@ void launch_dna_backward(const float* dy, const float* x, const float* mean, con
                          const float* scale, float* dx, int64_t planes, int64_t s, float slope,
                          hipStream_t stream);
 
+// bf16 storage (the 16 bits of each element; f32 arithmetic, stores round to nearest even).
+// The saved mean / rstd / scale stay fp32.
+typedef uint16_t bf16_bits;
+void launch_dna_forward(const bf16_bits* x, bf16_bits* y, float* mean, float* rstd, float* scale,
+                        int64_t planes, int64_t s, float p, float eps, float slope,
+                        uint64_t seed, uint64_t offset, bool dropout, const int64_t* rng,
+                        hipStream_t stream);
+void launch_dna_backward(const bf16_bits* dy, const bf16_bits* x, const float* mean,
+                         const float* rstd, const float* scale, bf16_bits* dx, int64_t planes,
+                         int64_t s, float slope, hipStream_t stream);
+
+// The instance the launchers above pick for a plane of `s` elements of `elem_bytes` (4 or 2)
+// whose operand addresses or-ed together are `ptr_bits` (host only): out = (GROUP, V, form),
+// form 0 scalar, 1 vector, 2 streaming.
+void dna_plan(int64_t s, int elem_bytes, uintptr_t ptr_bits, int64_t (&out)[3]);
+
 // Elementwise inverted dropout with explicit Philox (seed, offset); the mask is
 // regenerated in backward instead of stored.
 void launch_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset,
@@ -420,5 +436,16 @@ void launch_maxpool2x2_forward(const float* x, const float* add, float* y, int64
                                int w, hipStream_t stream);
 void launch_maxpool2x2_backward(const float* x, const float* dy, float* dx, int64_t planes,
                                 int channels, int h, int w, int64_t dy_img, hipStream_t stream);
+// The same four on bf16 storage: block sums and `m + add` in f32, rounded once on the store;
+// ties and NaN as in fp32.  Pair accesses need 4-byte aligned x rows / dy slices.
+void launch_up2x_cat(const bf16_bits* x, const bf16_bits* skip, bf16_bits* out, int64_t n,
+                     int c1, int c2, int h, int w, hipStream_t stream);
+void launch_up2x_backward(const bf16_bits* dy, bf16_bits* dx, int64_t n, int c, int h, int w,
+                          int64_t dy_img, hipStream_t stream);
+void launch_maxpool2x2_forward(const bf16_bits* x, const bf16_bits* add, bf16_bits* y,
+                               int64_t planes, int h, int w, hipStream_t stream);
+void launch_maxpool2x2_backward(const bf16_bits* x, const bf16_bits* dy, bf16_bits* dx,
+                                int64_t planes, int channels, int h, int w, int64_t dy_img,
+                                hipStream_t stream);
 
 }  // namespace tgpipe

@@ -49,8 +49,19 @@ inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) 
 //   VEC:   (k*GROUP + t)*4 + j          (16-byte coalesced)
 //   !VEC:  (k*4 + j)*GROUP + t          (4-byte coalesced, any S)
 // ---------------------------------------------------------------------------------------------
+// bf16 planes (E = __bf16): the same tiles and slots, a slot being 4 bf16 -- one 8-byte
+// access per lane in the VEC form -- so the U-Net planes 6^2 ... 192^2 fill their slots as they
+// do in fp32 and the (GROUP, V) table below is shared.  (8 bf16 per lane, the 16-byte access,
+// would need a table of its own with V = 9 -> 4.5: the U-Net planes are 9 * 4^k elements, so
+// no power-of-two group fills 8-wide slots.)  Storage only: a plane is held and reduced as
+// f32, and stores convert round-to-nearest-even.
 template <int GROUP>
 constexpr int kPlaneBlock = GROUP >= 256 ? GROUP : 256;
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(__bf16 v) { return static_cast<float>(v); }
 
 template <int GROUP, int V, bool VEC>
 struct PlaneTile {
@@ -105,6 +116,49 @@ struct PlaneTile {
     }
   }
 
+  __device__ static __forceinline__ void load(const __bf16* __restrict__ p, int t, int64_t s,
+                                              bool active, float (&r)[V * 4]) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (VEC) {
+        const int64_t idx = index(t, k, 0);
+        bf16x4 v = {0, 0, 0, 0};
+        if (active && idx < s) v = *reinterpret_cast<const bf16x4*>(p + idx);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[k * 4 + j] = static_cast<float>(v[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int64_t idx = index(t, k, j);
+          r[k * 4 + j] = (active && idx < s) ? static_cast<float>(p[idx]) : 0.f;
+        }
+      }
+    }
+  }
+
+  __device__ static __forceinline__ void store(__bf16* __restrict__ p, int t, int64_t s,
+                                               bool active, const float (&r)[V * 4]) {
+    if (!active) return;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (VEC) {
+        const int64_t idx = index(t, k, 0);
+        if (idx < s) {
+          bf16x4 v;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = static_cast<__bf16>(r[k * 4 + j]);
+          *reinterpret_cast<bf16x4*>(p + idx) = v;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int64_t idx = index(t, k, j);
+          if (idx < s) p[idx] = static_cast<__bf16>(r[k * 4 + j]);
+        }
+      }
+    }
+  }
+
   __device__ static __forceinline__ bool valid(int t, int k, int j, int64_t s) {
     return index(t, k, j) < s;
   }
@@ -143,9 +197,9 @@ __device__ __forceinline__ float plane_dropout_scale(int64_t plane, float p, uin
   return u >= p ? 1.f / (1.f - p) : 0.f;
 }
 
-template <int GROUP, int V, bool VEC>
+template <int GROUP, int V, bool VEC, typename E>
 __global__ __launch_bounds__(kPlaneBlock<GROUP>) void dna_forward_kernel(
-    const float* __restrict__ x, float* __restrict__ y, float* __restrict__ mean_out,
+    const E* __restrict__ x, E* __restrict__ y, float* __restrict__ mean_out,
     float* __restrict__ rstd_out, float* __restrict__ scale_out, int64_t planes, int64_t s,
     float p, float eps, float slope, uint64_t seed, uint64_t offset, bool dropout,
     const int64_t* __restrict__ rng) {
@@ -155,7 +209,7 @@ __global__ __launch_bounds__(kPlaneBlock<GROUP>) void dna_forward_kernel(
   const int t = threadIdx.x % GROUP;
   const int64_t plane = static_cast<int64_t>(blockIdx.x) * T::kPlanesPerBlock + threadIdx.x / GROUP;
   const bool active = plane < planes;
-  const float* xp = x + (active ? plane : 0) * s;
+  const E* xp = x + (active ? plane : 0) * s;
 
   float r[V * 4];
   T::load(xp, t, s, active, r);
@@ -192,10 +246,10 @@ __global__ __launch_bounds__(kPlaneBlock<GROUP>) void dna_forward_kernel(
   }
 }
 
-template <int GROUP, int V, bool VEC>
+template <int GROUP, int V, bool VEC, typename E>
 __global__ __launch_bounds__(kPlaneBlock<GROUP>) void dna_backward_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean_in,
-    const float* __restrict__ rstd_in, const float* __restrict__ scale_in, float* __restrict__ dx,
+    const E* __restrict__ dy, const E* __restrict__ x, const float* __restrict__ mean_in,
+    const float* __restrict__ rstd_in, const float* __restrict__ scale_in, E* __restrict__ dx,
     int64_t planes, int64_t s, float slope) {
   using T = PlaneTile<GROUP, V, VEC>;
   __shared__ float lds[T::kBlock / kWave];
@@ -233,32 +287,33 @@ __global__ __launch_bounds__(kPlaneBlock<GROUP>) void dna_backward_kernel(
 // Planes larger than one register tile: three streaming passes per plane.
 constexpr int kBigGroup = 1024;
 
+template <typename E>
 __global__ __launch_bounds__(kBigGroup) void dna_forward_big_kernel(
-    const float* __restrict__ x, float* __restrict__ y, float* __restrict__ mean_out,
+    const E* __restrict__ x, E* __restrict__ y, float* __restrict__ mean_out,
     float* __restrict__ rstd_out, float* __restrict__ scale_out, int64_t s, float p, float eps,
     float slope, uint64_t seed, uint64_t offset, bool dropout, const int64_t* __restrict__ rng) {
   __shared__ float lds[kBigGroup / kWave];
   philox_resolve(rng, seed, offset);
   using T = PlaneTile<kBigGroup, 1, false>;
   const int64_t plane = blockIdx.x;
-  const float* xp = x + plane * s;
+  const E* xp = x + plane * s;
   float acc = 0.f;
-  for (int64_t i = threadIdx.x; i < s; i += kBigGroup) acc += xp[i];
+  for (int64_t i = threadIdx.x; i < s; i += kBigGroup) acc += to_f32(xp[i]);
   const float inv_s = 1.f / static_cast<float>(s);
   const float mean = T::reduce(acc, lds) * inv_s;
   float sq = 0.f;
   for (int64_t i = threadIdx.x; i < s; i += kBigGroup) {
-    const float d = xp[i] - mean;
+    const float d = to_f32(xp[i]) - mean;
     sq += d * d;
   }
   const float var = T::reduce(sq, lds) * inv_s;
   const float scale = plane_dropout_scale(plane, p, seed, offset, dropout);
   const float rstd = rsqrtf(scale * scale * var + eps);
   const float mul = scale * rstd;
-  float* yp = y + plane * s;
+  E* yp = y + plane * s;
   for (int64_t i = threadIdx.x; i < s; i += kBigGroup) {
-    const float z = (xp[i] - mean) * mul;
-    yp[i] = z > 0.f ? z : z * slope;
+    const float z = (to_f32(xp[i]) - mean) * mul;
+    yp[i] = static_cast<E>(z > 0.f ? z : z * slope);
   }
   if (threadIdx.x == 0) {
     mean_out[plane] = mean;
@@ -267,32 +322,35 @@ __global__ __launch_bounds__(kBigGroup) void dna_forward_big_kernel(
   }
 }
 
+template <typename E>
 __global__ __launch_bounds__(kBigGroup) void dna_backward_big_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean_in,
-    const float* __restrict__ rstd_in, const float* __restrict__ scale_in, float* __restrict__ dx,
+    const E* __restrict__ dy, const E* __restrict__ x, const float* __restrict__ mean_in,
+    const float* __restrict__ rstd_in, const float* __restrict__ scale_in, E* __restrict__ dx,
     int64_t s, float slope) {
   __shared__ float lds[kBigGroup / kWave];
   using T = PlaneTile<kBigGroup, 1, false>;
   const int64_t plane = blockIdx.x;
   const float mean = mean_in[plane];
   const float mul = scale_in[plane] * rstd_in[plane];
-  const float* xp = x + plane * s;
-  const float* gp = dy + plane * s;
+  const E* xp = x + plane * s;
+  const E* gp = dy + plane * s;
   float sg = 0.f, sgz = 0.f;
   for (int64_t i = threadIdx.x; i < s; i += kBigGroup) {
-    const float z = (xp[i] - mean) * mul;
-    const float g = z > 0.f ? gp[i] : gp[i] * slope;
+    const float z = (to_f32(xp[i]) - mean) * mul;
+    const float gi = to_f32(gp[i]);
+    const float g = z > 0.f ? gi : gi * slope;
     sg += g;
     sgz += g * z;
   }
   const float inv_s = 1.f / static_cast<float>(s);
   const float mg = T::reduce(sg, lds) * inv_s;
   const float mgz = T::reduce(sgz, lds) * inv_s;
-  float* dp = dx + plane * s;
+  E* dp = dx + plane * s;
   for (int64_t i = threadIdx.x; i < s; i += kBigGroup) {
-    const float z = (xp[i] - mean) * mul;
-    const float g = z > 0.f ? gp[i] : gp[i] * slope;
-    dp[i] = mul * (g - mg - z * mgz);
+    const float z = (to_f32(xp[i]) - mean) * mul;
+    const float gi = to_f32(gp[i]);
+    const float g = z > 0.f ? gi : gi * slope;
+    dp[i] = static_cast<E>(mul * (g - mg - z * mgz));
   }
 }
 
@@ -373,24 +431,24 @@ __global__ __launch_bounds__(256) void segments_copy_kernel(SegmentTable table) 
   }
 }
 
-template <int GROUP, int V, bool VEC>
-void dna_fwd_launch(const float* x, float* y, float* mean, float* rstd, float* scale,
+template <int GROUP, int V, bool VEC, typename E>
+void dna_fwd_launch(const E* x, E* y, float* mean, float* rstd, float* scale,
                     int64_t planes, int64_t s, float p, float eps, float slope, uint64_t seed,
                     uint64_t offset, bool dropout, const int64_t* rng, hipStream_t stream) {
   using T = PlaneTile<GROUP, V, VEC>;
   const int grid = ceil_div(planes, T::kPlanesPerBlock);
-  hipLaunchKernelGGL((dna_forward_kernel<GROUP, V, VEC>), dim3(grid), dim3(T::kBlock), 0, stream,
+  hipLaunchKernelGGL((dna_forward_kernel<GROUP, V, VEC, E>), dim3(grid), dim3(T::kBlock), 0, stream,
                      x, y, mean, rstd, scale, planes, s, p, eps, slope, seed, offset, dropout,
                      rng);
 }
 
-template <int GROUP, int V, bool VEC>
-void dna_bwd_launch(const float* dy, const float* x, const float* mean, const float* rstd,
-                    const float* scale, float* dx, int64_t planes, int64_t s, float slope,
+template <int GROUP, int V, bool VEC, typename E>
+void dna_bwd_launch(const E* dy, const E* x, const float* mean, const float* rstd,
+                    const float* scale, E* dx, int64_t planes, int64_t s, float slope,
                     hipStream_t stream) {
   using T = PlaneTile<GROUP, V, VEC>;
   const int grid = ceil_div(planes, T::kPlanesPerBlock);
-  hipLaunchKernelGGL((dna_backward_kernel<GROUP, V, VEC>), dim3(grid), dim3(T::kBlock), 0,
+  hipLaunchKernelGGL((dna_backward_kernel<GROUP, V, VEC, E>), dim3(grid), dim3(T::kBlock), 0,
                      stream, dy, x, mean, rstd, scale, dx, planes, s, slope);
 }
 
@@ -411,23 +469,34 @@ void dna_bwd_launch(const float* dy, const float* x, const float* mean, const fl
     LAUNCH<1024, 9, VEC>(__VA_ARGS__);                             \
   }
 
-}  // namespace
-
 constexpr int64_t kDnaMaxTile = 1024 * 9 * 4;
 
-void launch_dna_forward(const float* x, float* y, float* mean, float* rstd, float* scale,
-                        int64_t planes, int64_t s, float p, float eps, float slope,
-                        uint64_t seed, uint64_t offset, bool dropout, const int64_t* rng,
-                        hipStream_t stream) {
+// The vector form needs whole slots (4 elements) and slot-aligned pointers: 16 bytes in fp32,
+// 8 bytes in bf16.  `ptr_bits`: the operands' addresses or-ed together.
+inline bool dna_vec_ok(int64_t s, uintptr_t ptr_bits, size_t elem_bytes) {
+  return (s % 4 == 0) && ((ptr_bits & (4 * elem_bytes - 1)) == 0);
+}
+
+template <int GROUP, int V, bool VEC>
+void dna_plan_record(int64_t (&out)[3]) {
+  out[0] = GROUP;
+  out[1] = V;
+  out[2] = VEC ? 1 : 0;
+}
+
+template <typename E>
+void dna_forward_any(const E* x, E* y, float* mean, float* rstd, float* scale, int64_t planes,
+                     int64_t s, float p, float eps, float slope, uint64_t seed, uint64_t offset,
+                     bool dropout, const int64_t* rng, hipStream_t stream) {
   if (planes == 0 || s == 0) return;
   if (s > kDnaMaxTile) {
-    hipLaunchKernelGGL(dna_forward_big_kernel, dim3(static_cast<unsigned>(planes)),
+    hipLaunchKernelGGL(dna_forward_big_kernel<E>, dim3(static_cast<unsigned>(planes)),
                        dim3(kBigGroup), 0, stream, x, y, mean, rstd, scale, s, p, eps, slope,
                        seed, offset, dropout, rng);
     return;
   }
-  const bool vec = (s % 4 == 0) && (((reinterpret_cast<uintptr_t>(x) |
-                                      reinterpret_cast<uintptr_t>(y)) & 15) == 0);
+  const bool vec = dna_vec_ok(
+      s, reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y), sizeof(E));
   if (vec) {
     TGPIPE_DNA_DISPATCH(dna_fwd_launch, true, x, y, mean, rstd, scale, planes, s, p, eps, slope,
                         seed, offset, dropout, rng, stream)
@@ -437,18 +506,19 @@ void launch_dna_forward(const float* x, float* y, float* mean, float* rstd, floa
   }
 }
 
-void launch_dna_backward(const float* dy, const float* x, const float* mean, const float* rstd,
-                         const float* scale, float* dx, int64_t planes, int64_t s, float slope,
-                         hipStream_t stream) {
+template <typename E>
+void dna_backward_any(const E* dy, const E* x, const float* mean, const float* rstd,
+                      const float* scale, E* dx, int64_t planes, int64_t s, float slope,
+                      hipStream_t stream) {
   if (planes == 0 || s == 0) return;
   if (s > kDnaMaxTile) {
-    hipLaunchKernelGGL(dna_backward_big_kernel, dim3(static_cast<unsigned>(planes)),
+    hipLaunchKernelGGL(dna_backward_big_kernel<E>, dim3(static_cast<unsigned>(planes)),
                        dim3(kBigGroup), 0, stream, dy, x, mean, rstd, scale, dx, s, slope);
     return;
   }
-  const bool vec = (s % 4 == 0) && (((reinterpret_cast<uintptr_t>(x) |
-                                      reinterpret_cast<uintptr_t>(dy) |
-                                      reinterpret_cast<uintptr_t>(dx)) & 15) == 0);
+  const bool vec = dna_vec_ok(s, reinterpret_cast<uintptr_t>(x) |
+                                     reinterpret_cast<uintptr_t>(dy) |
+                                     reinterpret_cast<uintptr_t>(dx), sizeof(E));
   if (vec) {
     TGPIPE_DNA_DISPATCH(dna_bwd_launch, true, dy, x, mean, rstd, scale, dx, planes, s, slope,
                         stream)
@@ -456,6 +526,51 @@ void launch_dna_backward(const float* dy, const float* x, const float* mean, con
     TGPIPE_DNA_DISPATCH(dna_bwd_launch, false, dy, x, mean, rstd, scale, dx, planes, s, slope,
                         stream)
   }
+}
+
+}  // namespace
+
+void dna_plan(int64_t s, int elem_bytes, uintptr_t ptr_bits, int64_t (&out)[3]) {
+  if (s > kDnaMaxTile) {
+    out[0] = kBigGroup;
+    out[1] = 0;
+    out[2] = 2;
+    return;
+  }
+  if (dna_vec_ok(s, ptr_bits, static_cast<size_t>(elem_bytes))) {
+    TGPIPE_DNA_DISPATCH(dna_plan_record, true, out)
+  } else {
+    TGPIPE_DNA_DISPATCH(dna_plan_record, false, out)
+  }
+}
+
+void launch_dna_forward(const float* x, float* y, float* mean, float* rstd, float* scale,
+                        int64_t planes, int64_t s, float p, float eps, float slope,
+                        uint64_t seed, uint64_t offset, bool dropout, const int64_t* rng,
+                        hipStream_t stream) {
+  dna_forward_any(x, y, mean, rstd, scale, planes, s, p, eps, slope, seed, offset, dropout, rng,
+                  stream);
+}
+
+void launch_dna_forward(const bf16_bits* x, bf16_bits* y, float* mean, float* rstd, float* scale,
+                        int64_t planes, int64_t s, float p, float eps, float slope,
+                        uint64_t seed, uint64_t offset, bool dropout, const int64_t* rng,
+                        hipStream_t stream) {
+  dna_forward_any(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), mean, rstd,
+                  scale, planes, s, p, eps, slope, seed, offset, dropout, rng, stream);
+}
+
+void launch_dna_backward(const float* dy, const float* x, const float* mean, const float* rstd,
+                         const float* scale, float* dx, int64_t planes, int64_t s, float slope,
+                         hipStream_t stream) {
+  dna_backward_any(dy, x, mean, rstd, scale, dx, planes, s, slope, stream);
+}
+
+void launch_dna_backward(const bf16_bits* dy, const bf16_bits* x, const float* mean,
+                         const float* rstd, const float* scale, bf16_bits* dx, int64_t planes,
+                         int64_t s, float slope, hipStream_t stream) {
+  dna_backward_any(reinterpret_cast<const __bf16*>(dy), reinterpret_cast<const __bf16*>(x), mean,
+                   rstd, scale, reinterpret_cast<__bf16*>(dx), planes, s, slope, stream);
 }
 
 void launch_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset,

@@ -20,6 +20,20 @@ namespace tgpipe {
 namespace {
 
 typedef float floatx2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// Element types: float, and __bf16 as storage -- sums and `m + add` are computed in f32 and
+// stored rounded to nearest even, once; comparisons on the upcast value are exact.
+template <typename E>
+struct Pair;
+template <>
+struct Pair<float> {
+  typedef floatx2 type;
+};
+template <>
+struct Pair<__bf16> {
+  typedef bf16x2 type;
+};
 
 unsigned grid_for(int64_t work) {
   const int64_t b = (work + 255) / 256;
@@ -27,10 +41,12 @@ unsigned grid_for(int64_t work) {
 }
 
 // One thread per pair of output columns (W even: the pair shares one upsampled source).
-__global__ __launch_bounds__(256) void up2x_cat_kernel(const float* __restrict__ x,
-                                                       const float* __restrict__ skip,
-                                                       float* __restrict__ out, int64_t n,
+template <typename E>
+__global__ __launch_bounds__(256) void up2x_cat_kernel(const E* __restrict__ x,
+                                                       const E* __restrict__ skip,
+                                                       E* __restrict__ out, int64_t n,
                                                        int c1, int c2, int h, int w) {
+  typedef typename Pair<E>::type P;
   const int H = 2 * h, W = 2 * w, ct = c1 + c2;
   const int64_t pairs = n * ct * H * w;  // output element pairs
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < pairs;
@@ -40,21 +56,23 @@ __global__ __launch_bounds__(256) void up2x_cat_kernel(const float* __restrict__
     const int oy = r / w, ox2 = r - oy * w;  // output row, column pair
     const int64_t img = plane / ct;
     const int ch = static_cast<int>(plane - img * ct);
-    floatx2 v;
+    P v;
     if (ch < c1) {
-      const float s = x[((img * c1 + ch) * h + (oy >> 1)) * w + ox2];
-      v = floatx2{s, s};
+      const E s = x[((img * c1 + ch) * h + (oy >> 1)) * w + ox2];
+      v = P{s, s};
     } else {
-      v = *reinterpret_cast<const floatx2*>(
+      v = *reinterpret_cast<const P*>(
           skip + ((img * c2 + (ch - c1)) * H + oy) * static_cast<int64_t>(W) + 2 * ox2);
     }
-    *reinterpret_cast<floatx2*>(out + (plane * H + oy) * static_cast<int64_t>(W) + 2 * ox2) = v;
+    *reinterpret_cast<P*>(out + (plane * H + oy) * static_cast<int64_t>(W) + 2 * ox2) = v;
   }
 }
 
-__global__ __launch_bounds__(256) void up2x_bwd_kernel(const float* __restrict__ dy,
-                                                       float* __restrict__ dx, int64_t n, int c,
+template <typename E>
+__global__ __launch_bounds__(256) void up2x_bwd_kernel(const E* __restrict__ dy,
+                                                       E* __restrict__ dx, int64_t n, int c,
                                                        int h, int w, int64_t dy_img) {
+  typedef typename Pair<E>::type P;
   const int W = 2 * w;
   const int64_t total = n * c * h * w;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < total;
@@ -63,10 +81,11 @@ __global__ __launch_bounds__(256) void up2x_bwd_kernel(const float* __restrict__
     const int r = static_cast<int>(i - plane * h * w);
     const int y = r / w, xx = r - y * w;
     const int64_t img = plane / c;
-    const float* g = dy + img * dy_img + ((plane - img * c) * 2 * h + 2 * y) * W + 2 * xx;
-    const floatx2 a = *reinterpret_cast<const floatx2*>(g);
-    const floatx2 b = *reinterpret_cast<const floatx2*>(g + W);
-    dx[i] = (a[0] + a[1]) + (b[0] + b[1]);
+    const E* g = dy + img * dy_img + ((plane - img * c) * 2 * h + 2 * y) * W + 2 * xx;
+    const P a = *reinterpret_cast<const P*>(g);
+    const P b = *reinterpret_cast<const P*>(g + W);
+    dx[i] = static_cast<E>((static_cast<float>(a[0]) + static_cast<float>(a[1])) +
+                           (static_cast<float>(b[0]) + static_cast<float>(b[1])));
   }
 }
 
@@ -86,9 +105,10 @@ __device__ __forceinline__ int argmax4(float v0, float v1, float v2, float v3, f
   return k;
 }
 
-__global__ __launch_bounds__(256) void maxpool2x2_fwd_kernel(const float* __restrict__ x,
-                                                             const float* __restrict__ add,
-                                                             float* __restrict__ y,
+template <typename E>
+__global__ __launch_bounds__(256) void maxpool2x2_fwd_kernel(const E* __restrict__ x,
+                                                             const E* __restrict__ add,
+                                                             E* __restrict__ y,
                                                              int64_t planes, int h, int w) {
   const int ho = h / 2, wo = w / 2;
   const int64_t total = planes * ho * wo;
@@ -97,10 +117,12 @@ __global__ __launch_bounds__(256) void maxpool2x2_fwd_kernel(const float* __rest
     const int64_t plane = i / (static_cast<int64_t>(ho) * wo);
     const int r = static_cast<int>(i - plane * ho * wo);
     const int oy = r / wo, ox = r - oy * wo;
-    const float* p = x + (plane * h + 2 * oy) * static_cast<int64_t>(w) + 2 * ox;
+    const E* p = x + (plane * h + 2 * oy) * static_cast<int64_t>(w) + 2 * ox;
     float m;
-    argmax4(p[0], p[1], p[w], p[w + 1], m);
-    y[i] = add != nullptr ? m + add[i] : m;  // AmoebaNet's cell-node sum folded in
+    argmax4(static_cast<float>(p[0]), static_cast<float>(p[1]), static_cast<float>(p[w]),
+            static_cast<float>(p[w + 1]), m);
+    // AmoebaNet's cell-node sum folded in
+    y[i] = static_cast<E>(add != nullptr ? m + static_cast<float>(add[i]) : m);
   }
 }
 
@@ -108,9 +130,10 @@ __global__ __launch_bounds__(256) void maxpool2x2_fwd_kernel(const float* __rest
 // so every input element is written exactly once (odd trailing rows / columns, which no
 // window covers, are zeroed by the caller's allocation).  dy may be a channel slice of a
 // larger gradient (image stride dy_img, e.g. AmoebaNet's concatenated cell output).
-__global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __restrict__ x,
-                                                             const float* __restrict__ dy,
-                                                             float* __restrict__ dx,
+template <typename E>
+__global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const E* __restrict__ x,
+                                                             const E* __restrict__ dy,
+                                                             E* __restrict__ dx,
                                                              int64_t planes, int channels,
                                                              int h, int w, int64_t dy_img) {
   const int ho = h / 2, wo = w / 2;
@@ -121,16 +144,18 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __rest
     const int r = static_cast<int>(i - plane * ho * wo);
     const int oy = r / wo, ox = r - oy * wo;
     const int64_t base = (plane * h + 2 * oy) * static_cast<int64_t>(w) + 2 * ox;
-    const float* p = x + base;
+    const E* p = x + base;
     float m;
-    const int k = argmax4(p[0], p[1], p[w], p[w + 1], m);
+    const int k = argmax4(static_cast<float>(p[0]), static_cast<float>(p[1]),
+                          static_cast<float>(p[w]), static_cast<float>(p[w + 1]), m);
     const int64_t img = plane / channels;
-    const float g = dy[img * dy_img + (plane - img * channels) * ho * wo + r];
-    float* q = dx + base;
-    q[0] = k == 0 ? g : 0.f;
-    q[1] = k == 1 ? g : 0.f;
-    q[w] = k == 2 ? g : 0.f;
-    q[w + 1] = k == 3 ? g : 0.f;
+    const E g = dy[img * dy_img + (plane - img * channels) * ho * wo + r];
+    const E zero = static_cast<E>(0.f);
+    E* q = dx + base;
+    q[0] = k == 0 ? g : zero;
+    q[1] = k == 1 ? g : zero;
+    q[w] = k == 2 ? g : zero;
+    q[w + 1] = k == 3 ? g : zero;
   }
 }
 
@@ -175,36 +200,84 @@ void launch_add_relu(const float* a, const float* b, float* y, int64_t total,
                      a, b, y, quads, total);
 }
 
-void launch_up2x_cat(const float* x, const float* skip, float* out, int64_t n, int c1, int c2,
-                     int h, int w, hipStream_t stream) {
+namespace {
+
+template <typename E>
+void up2x_cat_any(const E* x, const E* skip, E* out, int64_t n, int c1, int c2, int h, int w,
+                  hipStream_t stream) {
   const int64_t pairs = n * (c1 + c2) * 2 * static_cast<int64_t>(h) * w;
   if (pairs == 0) return;
-  hipLaunchKernelGGL(up2x_cat_kernel, dim3(grid_for(pairs)), dim3(256), 0, stream, x, skip, out,
-                     n, c1, c2, h, w);
+  hipLaunchKernelGGL(up2x_cat_kernel<E>, dim3(grid_for(pairs)), dim3(256), 0, stream, x, skip,
+                     out, n, c1, c2, h, w);
+}
+
+template <typename E>
+void up2x_backward_any(const E* dy, E* dx, int64_t n, int c, int h, int w, int64_t dy_img,
+                       hipStream_t stream) {
+  const int64_t total = n * c * static_cast<int64_t>(h) * w;
+  if (total == 0) return;
+  hipLaunchKernelGGL(up2x_bwd_kernel<E>, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, n,
+                     c, h, w, dy_img);
+}
+
+template <typename E>
+void maxpool2x2_forward_any(const E* x, const E* add, E* y, int64_t planes, int h, int w,
+                            hipStream_t stream) {
+  const int64_t total = planes * (h / 2) * static_cast<int64_t>(w / 2);
+  if (total == 0) return;
+  hipLaunchKernelGGL(maxpool2x2_fwd_kernel<E>, dim3(grid_for(total)), dim3(256), 0, stream, x,
+                     add, y, planes, h, w);
+}
+
+template <typename E>
+void maxpool2x2_backward_any(const E* x, const E* dy, E* dx, int64_t planes, int channels, int h,
+                             int w, int64_t dy_img, hipStream_t stream) {
+  const int64_t total = planes * (h / 2) * static_cast<int64_t>(w / 2);
+  if (total == 0) return;
+  hipLaunchKernelGGL(maxpool2x2_bwd_kernel<E>, dim3(grid_for(total)), dim3(256), 0, stream, x,
+                     dy, dx, planes, channels, h, w, dy_img);
+}
+
+const __bf16* bf(const bf16_bits* p) { return reinterpret_cast<const __bf16*>(p); }
+__bf16* bf(bf16_bits* p) { return reinterpret_cast<__bf16*>(p); }
+
+}  // namespace
+
+void launch_up2x_cat(const float* x, const float* skip, float* out, int64_t n, int c1, int c2,
+                     int h, int w, hipStream_t stream) {
+  up2x_cat_any(x, skip, out, n, c1, c2, h, w, stream);
+}
+void launch_up2x_cat(const bf16_bits* x, const bf16_bits* skip, bf16_bits* out, int64_t n,
+                     int c1, int c2, int h, int w, hipStream_t stream) {
+  up2x_cat_any(bf(x), bf(skip), bf(out), n, c1, c2, h, w, stream);
 }
 
 void launch_up2x_backward(const float* dy, float* dx, int64_t n, int c, int h, int w,
                           int64_t dy_img, hipStream_t stream) {
-  const int64_t total = n * c * static_cast<int64_t>(h) * w;
-  if (total == 0) return;
-  hipLaunchKernelGGL(up2x_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dy, dx, n, c,
-                     h, w, dy_img);
+  up2x_backward_any(dy, dx, n, c, h, w, dy_img, stream);
+}
+void launch_up2x_backward(const bf16_bits* dy, bf16_bits* dx, int64_t n, int c, int h, int w,
+                          int64_t dy_img, hipStream_t stream) {
+  up2x_backward_any(bf(dy), bf(dx), n, c, h, w, dy_img, stream);
 }
 
 void launch_maxpool2x2_forward(const float* x, const float* add, float* y, int64_t planes, int h,
                                int w, hipStream_t stream) {
-  const int64_t total = planes * (h / 2) * static_cast<int64_t>(w / 2);
-  if (total == 0) return;
-  hipLaunchKernelGGL(maxpool2x2_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, add,
-                     y, planes, h, w);
+  maxpool2x2_forward_any(x, add, y, planes, h, w, stream);
+}
+void launch_maxpool2x2_forward(const bf16_bits* x, const bf16_bits* add, bf16_bits* y,
+                               int64_t planes, int h, int w, hipStream_t stream) {
+  maxpool2x2_forward_any(bf(x), bf(add), bf(y), planes, h, w, stream);
 }
 
 void launch_maxpool2x2_backward(const float* x, const float* dy, float* dx, int64_t planes,
                                 int channels, int h, int w, int64_t dy_img, hipStream_t stream) {
-  const int64_t total = planes * (h / 2) * static_cast<int64_t>(w / 2);
-  if (total == 0) return;
-  hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, dy,
-                     dx, planes, channels, h, w, dy_img);
+  maxpool2x2_backward_any(x, dy, dx, planes, channels, h, w, dy_img, stream);
+}
+void launch_maxpool2x2_backward(const bf16_bits* x, const bf16_bits* dy, bf16_bits* dx,
+                                int64_t planes, int channels, int h, int w, int64_t dy_img,
+                                hipStream_t stream) {
+  maxpool2x2_backward_any(bf(x), bf(dy), bf(dx), planes, channels, h, w, dy_img, stream);
 }
 
 }  // namespace tgpipe

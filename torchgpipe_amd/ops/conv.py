@@ -47,6 +47,7 @@ from torch import Tensor, nn
 import torch.nn.functional as F
 
 from torchgpipe_amd.ops import _ext, gradacc, precision
+from torchgpipe_amd.ops.precision import autocast_lowp
 
 __all__ = ['WinogradConv2d', 'winograd_conv2d', 'wino_eligible', 'new_step',
            'clear_winograd_caches', 'cache_bytes', 'refresh_step_caches', 'hold_cache',
@@ -709,6 +710,7 @@ def wino_eligible(x: Tensor, weight: Tensor, stride: Sequence[int] = (1, 1),
                   groups: int = 1) -> bool:
     """Whether the HIP Winograd kernel computes this convolution."""
     return (WINOGRAD_ENABLED and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+            and not autocast_lowp('cuda')  # the library convolution then, which ATen casts
             and weight.shape[1] >= MIN_CHANNELS
             and weight.shape[0] * weight.shape[1] * 16 * 4 <= MAX_TRANSFORM_BYTES
             and weight.dtype == torch.float32 and tuple(weight.shape[2:]) == (3, 3)

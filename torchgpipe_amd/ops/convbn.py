@@ -52,6 +52,7 @@ import torch.nn.functional as F
 from torchgpipe_amd.batchnorm import DeferredBatchNorm
 from torchgpipe_amd.ops import _ext, gradacc
 from torchgpipe_amd.ops.conv import _TransformCache
+from torchgpipe_amd.ops.precision import autocast_lowp
 
 __all__ = ['relu_conv_bn', 'ReLUConvBN', 'FusedChain', 'conv_supported', 'fused_triplets',
            'fusable', 'disabled', 'GemmConv2d', 'gemm_conv2d', 'gemm_conv_eligible',
@@ -96,6 +97,8 @@ _BN_TYPES = (nn.BatchNorm2d, DeferredBatchNorm)
 def _bn_ok(bn: nn.Module, x: Tensor) -> bool:
     if not (bn.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
+    if autocast_lowp('cuda'):  # the fused fp32 ops step aside for the ATen ops autocast casts
+        return False
     if isinstance(bn, DeferredBatchNorm):
         # micro-batch statistics folded into its fp64 accumulator by the op's finalize; any
         # momentum (None too): the factor is applied at the commit (DeferredBatchNorm._commit)
@@ -114,7 +117,7 @@ def _bn_eval_ok(bn: nn.Module, x: Tensor, add: Optional[Tensor] = None) -> bool:
     normalising with its running statistics, and nothing that needs a gradient (the eval
     ops are forward-only)."""
     return (_ENABLED and isinstance(bn, _BN_TYPES) and not bn.training and x.is_cuda
-            and x.dtype == torch.float32 and x.dim() == 4
+            and x.dtype == torch.float32 and x.dim() == 4 and not autocast_lowp('cuda')
             and bn.track_running_stats and bn.running_mean is not None
             and bn.running_var is not None
             and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device
@@ -364,7 +367,7 @@ def eval_fusable(x: Tensor, convs: Sequence[nn.Conv2d], bn: nn.Module,
 
 def _convs_ok(x: Tensor, convs: Sequence[nn.Conv2d]) -> bool:
     numel = x.numel()
-    if numel * 4 >= _LIMIT:
+    if numel * 4 >= _LIMIT or autocast_lowp('cuda'):
         return False
     co = 0
     for c in convs:
@@ -634,6 +637,7 @@ def gemm_conv_eligible(x: Tensor, conv: nn.Conv2d) -> bool:
     limit = (1 << 31) - 64  # 32-bit buffer offsets of the kernels
     out_numel = x.numel() // max(1, x.shape[1]) * conv.out_channels if x.dim() == 4 else 0
     return (_ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and not autocast_lowp('cuda')
             and x.numel() * 4 < limit and conv.weight.numel() * 4 < limit
             and out_numel * 4 < limit
             and conv.weight.dtype == torch.float32 and conv.bias is None and conv.groups == 1

@@ -13,8 +13,10 @@ The Dropout2d channel mask comes from Philox4x32-10 with an explicit
 ``(seed, offset)`` (``utils.rng.philox_pair``): replayed bit-exactly under
 checkpoint recomputation through the cell's RNG tape.
 
-CPU tensors (and non-fp32 dtypes) use a PyTorch composite with the same
-Philox mask — the oracle of the kernel tests.
+The kernel follows the input dtype: fp32, or bf16 storage with f32 arithmetic (the plane
+is held and reduced as f32, the saved statistics stay fp32, stores round to nearest even),
+with or without ``torch.autocast``.  CPU tensors and other dtypes use a PyTorch composite
+with the same Philox mask — the oracle of the kernel tests.
 """
 from typing import Optional, Tuple
 
@@ -27,6 +29,10 @@ from torchgpipe_amd.ops.philox import philox4x32_10, to_uniform
 from torchgpipe_amd.utils.rng import philox_draw
 
 __all__ = ['drop_norm_act', 'DropNormAct', 'plane_scale_reference']
+
+
+# dtypes the HIP kernel takes as they come (csrc/kernels.hip K3 / K3b)
+_NATIVE_DTYPES = (torch.float32, torch.bfloat16)
 
 
 def _signed64(v: int) -> int:
@@ -65,6 +71,8 @@ class _DropNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor) -> Tuple:  # type: ignore[override]
         x, mean, rstd, scale = ctx.saved_tensors
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
         dx = _ext.require(dy).dna_backward(dy, x, mean, rstd, scale, ctx.slope)
         return dx, None, None, None, None, None, None, None
 
@@ -75,11 +83,12 @@ def drop_norm_act(x: Tensor, p: float = 0.1, training: bool = True, eps: float =
     dropout = training and p > 0.0
     n, c = x.shape[:2]
     seed, offset, rng = philox_draw(x.device, n * c) if dropout else (0, 0, None)
-    if x.is_cuda and x.dtype == torch.float32:
+    if x.is_cuda and x.dtype in _NATIVE_DTYPES:
         return _DropNormAct.apply(x.contiguous(), float(p), float(eps), float(slope),
                                   _signed64(seed), _signed64(offset), dropout, rng)
     if rng is not None:
-        raise RuntimeError('drop_norm_act: a device Philox slot needs the fp32 GPU kernel')
+        raise RuntimeError('drop_norm_act: a device Philox slot needs the GPU kernel '
+                           f'(fp32 or bf16 input, got {x.dtype})')
     return _composite(x, p, eps, slope, seed, offset, dropout)
 
 

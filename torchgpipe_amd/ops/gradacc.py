@@ -47,6 +47,8 @@ import weakref
 import torch
 from torch import Tensor
 
+from torchgpipe_amd.ops.precision import autocast_lowp
+
 __all__ = ['target', 'commit', 'enabled', 'release', 'deferred_wgrad', 'slab', 'deferred',
            'flush_pending', 'pending_snapshot', 'register_pending', 'library_conv2d',
            'linear']
@@ -315,7 +317,7 @@ def library_conv2d(x: Tensor, conv: torch.nn.Conv2d) -> Tensor:
     """``conv(x)`` on the library convolution with the gradient accumulation fused (GPU,
     zero padding); ``conv.forward`` otherwise."""
     if not (_ENABLED and x.is_cuda and conv.padding_mode == 'zeros'
-            and isinstance(conv.padding, tuple)):
+            and isinstance(conv.padding, tuple)) or autocast_lowp('cuda'):
         return torch.nn.Conv2d.forward(conv, x)
     return _LibraryConv.apply(x, conv.weight, conv.bias, conv.stride, conv.padding,
                               conv.dilation, conv.groups)
@@ -356,6 +358,6 @@ class _Linear(torch.autograd.Function):
 
 def linear(x: Tensor, layer: torch.nn.Linear) -> Tensor:
     """``layer(x)`` with the gradient accumulation fused (GPU); ``layer.forward`` otherwise."""
-    if not (_ENABLED and x.is_cuda):
+    if not (_ENABLED and x.is_cuda) or autocast_lowp('cuda'):
         return torch.nn.Linear.forward(layer, x)
     return _Linear.apply(x, layer.weight, layer.bias)

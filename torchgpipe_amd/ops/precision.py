@@ -37,7 +37,7 @@ from torch import Tensor
 import torch.nn.functional as F
 
 __all__ = ['LEVELS', 'set_conv_precision', 'get_conv_precision', 'conv_precision',
-           'split_bf16', 'reference_conv2d', 'reference_conv2d_backward']
+           'autocast_lowp', 'split_bf16', 'reference_conv2d', 'reference_conv2d_backward']
 
 LEVELS = ('highest', 'high', 'medium')
 
@@ -79,6 +79,15 @@ def conv_precision(level: str) -> Iterator[None]:
         yield
     finally:
         set_conv_precision(before)
+
+
+def autocast_lowp(device_type: str) -> bool:
+    """Whether ``torch.autocast`` is enabled on this thread for ``device_type`` with a dtype
+    other than fp32.  The native fp32 ops that replace an ATen op on autocast's
+    lower-precision list (convolutions, linear) step aside when it is: their modules run
+    the plain ``nn`` forward, which ATen casts.  ``set_conv_precision`` has no say there."""
+    return torch.is_autocast_enabled(device_type) and \
+        torch.get_autocast_dtype(device_type) != torch.float32
 
 
 def split_bf16(t: Tensor) -> Tuple[Tensor, Tensor, Tensor]:

@@ -7,7 +7,10 @@
 * :class:`MaxPool2x2` -- ``nn.MaxPool2d(2, stride=2)`` without ATen's int64 index tensor;
   the backward re-finds each window's argmax from the input (ATen's tie / NaN order).
 
-Both fall back to the PyTorch ops off the GPU, for other dtypes and odd shapes.
+Both follow the input dtype -- fp32, or bf16 storage with f32 arithmetic where there is any
+(the backward's 2x2 block sum, ``pool(x) + add``), rounded once on the store -- when every
+operand has that dtype, with or without ``torch.autocast``.  They fall back to the PyTorch
+ops off the GPU, for other or mixed dtypes and odd shapes.
 """
 from typing import Optional, Tuple
 
@@ -24,17 +27,24 @@ class _Up2xCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, skip: Tensor) -> Tensor:  # type: ignore[override]
         ctx.c1 = x.shape[1]
+        ctx.dtype = x.dtype
         return _ext.require(x).up2x_cat_forward(x, skip)
 
     @staticmethod
     def backward(ctx, dy: Tensor) -> Tuple[Tensor, Tensor]:  # type: ignore[override]
+        if dy.dtype != ctx.dtype:
+            dy = dy.to(ctx.dtype)
         dx = _ext.require(dy).up2x_backward(dy, ctx.c1)
         return dx, dy[:, ctx.c1:]
 
 
+_NATIVE_DTYPES = (torch.float32, torch.bfloat16)
+
+
 def _fusable(*ts: Tensor) -> bool:
-    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 for t in ts) \
-        and _ext.available()
+    """GPU NCHW tensors of one dtype the kernels take (fp32 or bf16)."""
+    return all(t.is_cuda and t.dtype == ts[0].dtype and t.dim() == 4 for t in ts) \
+        and ts[0].dtype in _NATIVE_DTYPES and _ext.available()
 
 
 def up2x_cat(x: Tensor, skip: Tensor) -> Tensor:
@@ -62,6 +72,8 @@ class _MaxPool2x2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor):  # type: ignore[override]
         (x,) = ctx.saved_tensors
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
         return _ext.require(dy).maxpool2x2_backward(x, dy), dy if ctx.has_add else None
 
 
@@ -77,7 +89,7 @@ class MaxPool2x2(nn.MaxPool2d):
 
     def forward(self, x: Tensor, add: Optional[Tensor] = None) -> Tensor:  # type: ignore[override]
         if _fusable(x) and not self.return_indices and not self.ceil_mode and \
-                (add is None or _fusable(add)):
+                (add is None or _fusable(x, add)):
             return _MaxPool2x2.apply(x, add)
         out = super().forward(x)
         return out if add is None else out + add

@@ -63,7 +63,7 @@ from torch import Tensor, nn
 
 from torchgpipe_amd.checkpoint import enable_checkpointing, enable_recomputing
 from torchgpipe_amd.ops import gradacc
-from torchgpipe_amd.utils import rng
+from torchgpipe_amd.utils import autocast, rng
 
 __all__ = ['Segments', 'SegmentCell']
 
@@ -126,11 +126,16 @@ class Segments:
         cells: number of micro-batches (each gets its graphs).
         stop: the first ``stop`` micro-batches are checkpointed.
         warmup: eager steps before the capture step.
+        amp: the autocast state of the steps these cells serve (the stage keys its
+            ``Segments`` on it).  Every capture body runs under it -- the recomputation's
+            too, which is captured from ``backward()``, usually outside the user's
+            autocast block -- with the weight-cast cache off.
     """
 
     def __init__(self, partition: nn.Module, device: torch.device, cells: int, stop: int,
-                 warmup: int = 1) -> None:
+                 warmup: int = 1, amp: Optional[autocast.AutocastState] = None) -> None:
         self.partition = partition
+        self.amp = amp if amp is not None else autocast.capture()
         self.device = device
         self.warmup = warmup
         self.steps = 0
@@ -266,14 +271,15 @@ class Segments:
             assert cell.slot is not None
             if cell.checkpointed:
                 with _capturing(graph, self.streams[k], self.pools[k]), torch.no_grad(), \
-                        enable_checkpointing(), rng.slot_scope(cell.slot):
+                        enable_checkpointing(), rng.slot_scope(cell.slot), \
+                        self.amp.entered(cache=False):
                     out = list(fn(tuple(cell.inputs)))
                 # as the outputs of an eager Checkpoint node: every float output
                 cell.out_grad = [t.is_floating_point() for t in out]
             else:
                 cell.leaves = [t.detach().requires_grad_(t.requires_grad) for t in cell.inputs]
                 with _capturing(graph, self.streams[k], self.pools[k]), torch.enable_grad(), \
-                        rng.slot_scope(cell.slot):
+                        rng.slot_scope(cell.slot), self.amp.entered(cache=False):
                     cell.rec_out = list(fn(tuple(cell.leaves)))
                 out = [t.detach() for t in cell.rec_out]
                 cell.out_grad = [t.requires_grad for t in cell.rec_out]
@@ -309,7 +315,8 @@ class Segments:
             cell.leaves = [t.detach().requires_grad_(t.requires_grad) for t in cell.inputs]
             assert cell.slot is not None
             with _capturing(graph, self.streams[k], self.pools[k]), torch.enable_grad(), \
-                    enable_recomputing(), rng.slot_scope(cell.slot):
+                    enable_recomputing(), rng.slot_scope(cell.slot), \
+                    self.amp.entered(cache=False):
                 cell.rec_out = list(fn(tuple(cell.leaves)))
             if cell.slot.delta != cell.increment:
                 raise RuntimeError(f'cell {i}: the recomputation drew {cell.slot.delta} Philox '

@@ -55,7 +55,7 @@ from torchgpipe_amd.skip.namespace import Namespace
 from torchgpipe_amd.skip.skippable import Skippable, verify_skippables
 from torchgpipe_amd.skip.tracker import SkipTracker, use_skip_tracker
 from torchgpipe_amd.stream import named_stream
-from torchgpipe_amd.utils import trace
+from torchgpipe_amd.utils import autocast, trace
 from torchgpipe_amd.utils.meta import is_meta
 from torchgpipe_amd.utils.meta import materialize as meta_materialize
 
@@ -423,6 +423,7 @@ class PipelineStage:
             OrderedRunningStats.for_module(self.partition) if self._stateful else None
         self._rec_slotted = False  # this step's recomputations are slotted
         self._sig: Optional[Signature] = None
+        self._amp = autocast.capture()  # the autocast state of the last forward()
         self._m = 0
         self._probe: Optional[List[Tuple[str, Any, Any]]] = None
         if graph_warmup < 1:
@@ -464,12 +465,14 @@ class PipelineStage:
         if not self.graph_cells or not self.training or \
                 not torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
             return None
-        key = (sig, stop)
+        # (the autocast state too: a cell captured without autocast must not be replayed
+        # for a step under it, or the reverse)
+        key = (sig, stop, self._amp)
         if self._segments is None or self._seg_key != key:
             from torchgpipe_amd.parallel.segments import Segments
             self._segments = Segments(self.partition, self.device,
                                       _micro_batch_count(sig, self.chunks), stop,
-                                      self.graph_warmup)
+                                      self.graph_warmup, self._amp)
             self._seg_key = key
         return self._segments
 
@@ -614,7 +617,12 @@ class PipelineStage:
         # Metadata cache key of one message.  Both endpoints are part of it: a
         # stage may send the same kind of message (skips, skip gradients) to
         # several peers in one micro-batch, each with its own layout.
-        return (self._sig, self.training, torch.is_grad_enabled(), kind, i, src, dst)
+        # The mode slot carries the forward's autocast state next to the grad mode (messages
+        # of a step under autocast have other dtypes); the forward's, since ``backward()``
+        # usually runs outside the block.  Seven fields, the kind fourth: stripes.message_kind.
+        mode = (torch.is_grad_enabled(), self._amp) if self._amp.any_enabled \
+            else torch.is_grad_enabled()
+        return (self._sig, self.training, mode, kind, i, src, dst)
 
     # -- forward ----------------------------------------------------------------------------
 
@@ -654,6 +662,7 @@ class PipelineStage:
         if input is not None:
             microbatch.check(input)
         wino_new_step()  # weights may have changed since the last step (even via .data)
+        self._amp = autocast.capture()
         sig = self._agree_signature(input, signature)
         if sig != self._sig:
             self._sig = sig

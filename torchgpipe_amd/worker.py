@@ -6,8 +6,9 @@ Difference by design: the reference spawns fresh threads on *every*
 ``GPipe.forward`` (``pipeline.py:112``).  Here a :class:`WorkerPool` keeps
 one persistent daemon thread per distinct device for the lifetime of the
 ``GPipe`` module (``spawn_workers`` is kept as a context manager for
-one-shot use and tests).  Each task carries its own grad mode so the
-persistent threads honour ``torch.no_grad()`` of the calling thread.
+one-shot use and tests).  Each task carries its own grad mode and autocast
+state so the persistent threads honour ``torch.no_grad()`` and
+``torch.autocast`` of the calling thread.
 
 Kernel launches are asynchronous, so a worker thread only spends host time
 enqueueing HIP work; the device threads let PyTorch issue launches for
@@ -26,6 +27,7 @@ import torch
 
 from torchgpipe_amd.microbatch import Batch
 from torchgpipe_amd.stream import AbstractStream, normalize_device, use_device, use_stream
+from torchgpipe_amd.utils import autocast
 
 __all__: List[str] = []
 
@@ -37,7 +39,7 @@ OutQueue = Queue
 class Task:
     """``compute`` runs on a worker thread; ``finalize`` on the scheduling thread."""
 
-    __slots__ = ('stream', '_compute', '_finalize', 'grad_mode')
+    __slots__ = ('stream', '_compute', '_finalize', 'grad_mode', 'autocast')
 
     def __init__(self, stream: AbstractStream, *,
                  compute: Callable[[], Batch],
@@ -46,6 +48,7 @@ class Task:
         self._compute = compute
         self._finalize = finalize
         self.grad_mode = torch.is_grad_enabled()
+        self.autocast = autocast.capture()
 
     def compute(self) -> Batch:
         with use_stream(self.stream):
@@ -69,7 +72,8 @@ def worker(in_queue: InQueue, out_queue: OutQueue, device: torch.device,
             if task is None:
                 break
             try:
-                with torch.set_grad_enabled(task.grad_mode if grad_mode is None else grad_mode):
+                with torch.set_grad_enabled(task.grad_mode if grad_mode is None else grad_mode), \
+                        task.autocast.entered():
                     batch = task.compute()
             except Exception:
                 out_queue.put((False, sys.exc_info()))
