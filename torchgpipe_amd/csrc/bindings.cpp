@@ -148,6 +148,70 @@ void copy_segments(at::TensorList srcs, at::TensorList dsts) {
   }
 }
 
+// The dense tensors of one dtype (fp32 or bf16) on one GPU that the gradient-clipping
+// kernels take, as spans; empty tensors are left out.  Returns the element size.
+int grad_spans(at::TensorList grads, const char* op, std::vector<GradSpan>& spans) {
+  int elem_bytes = 0;
+  const at::Tensor* like = nullptr;
+  for (const at::Tensor& g : grads) {
+    TORCH_CHECK(g.defined() && g.is_cuda(), op, " takes GPU tensors");
+    TORCH_CHECK(g.layout() == at::kStrided && g.is_non_overlapping_and_dense(), op,
+                " takes dense tensors");
+    TORCH_CHECK(g.scalar_type() == at::kFloat || g.scalar_type() == at::kBFloat16, op,
+                " takes float32 or bfloat16 tensors");
+    if (like == nullptr) like = &g;
+    TORCH_CHECK(g.device() == like->device() && g.scalar_type() == like->scalar_type(), op,
+                " takes tensors of one device and one dtype");
+    elem_bytes = static_cast<int>(g.element_size());
+    if (g.numel() > 0) spans.push_back({g.data_ptr(), g.numel()});
+  }
+  return elem_bytes;
+}
+
+void check_launched(const char* op) {
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, op, " failed to launch: ", hipGetErrorString(err));
+}
+
+at::Tensor grad_sumsq(at::TensorList grads) {
+  std::vector<GradSpan> spans;
+  const int elem_bytes = grad_spans(grads, "grad_sumsq", spans);
+  auto opts = at::TensorOptions().dtype(at::kDouble);
+  if (grads.empty()) return at::zeros({1}, opts.device(at::kCUDA));
+  const auto device = grads[0].device();
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  if (spans.empty()) return at::zeros({1}, opts.device(device));
+  const int count = static_cast<int>(spans.size());
+  // at::empty: the caching allocator's blocks are safe to take and drop under graph capture
+  auto partials = at::empty({grad_clip_blocks(spans.data(), count, elem_bytes)},
+                            opts.device(device));
+  auto out = at::empty({1}, opts.device(device));
+  launch_grad_sumsq(spans.data(), count, elem_bytes, partials.data_ptr<double>(),
+                    out.data_ptr<double>(), at::hip::getCurrentHIPStream(device.index()).stream());
+  check_launched("grad_sumsq");
+  return out;
+}
+
+void grad_scale_(at::TensorList grads, const at::Tensor& sumsq, double max_norm, double eps) {
+  std::vector<GradSpan> spans;
+  const int elem_bytes = grad_spans(grads, "grad_scale_", spans);
+  if (spans.empty()) return;
+  const auto device = grads[0].device();
+  TORCH_CHECK(sumsq.is_cuda() && sumsq.device() == device && sumsq.scalar_type() == at::kDouble &&
+                  sumsq.numel() >= 1,
+              "sumsq must be a float64 tensor on the gradients' device");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  launch_grad_scale(spans.data(), static_cast<int>(spans.size()), elem_bytes,
+                    sumsq.data_ptr<double>(), max_norm, eps,
+                    at::hip::getCurrentHIPStream(device.index()).stream());
+  check_launched("grad_scale_");
+}
+
+// (chunk elements fp32, chunk elements bf16, tensors per launch, threads per block)
+std::vector<int64_t> grad_clip_info() {
+  return {kGradClipChunkF32, kGradClipChunkBF16, kGradClipTensors, kGradClipThreads};
+}
+
 // `out` (optional): an existing transform of the same shape to overwrite in place (the
 // per-step cache refresh, ops/conv.py) instead of a new tensor plus a copy.
 at::Tensor transform_out(const c10::optional<at::Tensor>& out, at::IntArrayRef shape,
@@ -495,6 +559,10 @@ TORCH_LIBRARY(tgpipe, m) {
   m.def("philox_uniform(int n, int seed, int offset, Device device, Tensor? rng=None) -> Tensor");
   m.def("spin(int ns, Device device) -> ()");
   m.def("copy_segments(Tensor[] srcs, Tensor(a!)[] dsts) -> ()");
+  // global-norm gradient clipping: fp64 sum of squares [1], in-place scale reading it
+  m.def("grad_sumsq(Tensor[] grads) -> Tensor");
+  m.def("grad_scale_(Tensor(a!)[] grads, Tensor sumsq, float max_norm, float eps) -> ()");
+  m.def("grad_clip_info() -> int[]", &tgpipe::grad_clip_info);
   m.def("wino_weight(Tensor w, bool flip, Tensor? out=None) -> Tensor");
   m.def("wino_wgrad(Tensor x, Tensor dy, int splits=0, int variant=-1, Tensor? into=None) -> Tensor");
   m.def("wino_conv(Tensor x, Tensor u, Tensor? bias, int out_channels, int variant=-1, "
@@ -526,6 +594,7 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("dna_backward", &tgpipe::dna_backward);
   m.impl("dropout", &tgpipe::dropout);
   m.impl("copy_segments", &tgpipe::copy_segments);
+  m.impl("grad_scale_", &tgpipe::grad_scale_);
   m.impl("wino_weight", &tgpipe::wino_weight);
   m.impl("wino_conv", &tgpipe::wino_conv);
   m.impl("wino_wgrad", &tgpipe::wino_wgrad);
@@ -540,6 +609,7 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
 TORCH_LIBRARY_IMPL(tgpipe, CompositeExplicitAutograd, m) {
   m.impl("philox_uniform", &tgpipe::philox_uniform);
   m.impl("spin", &tgpipe::spin);
+  m.impl("grad_sumsq", &tgpipe::grad_sumsq);  // an empty list has no dispatch key
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

@@ -63,6 +63,25 @@ struct Segment {
 constexpr int kMaxSegments = 16;
 void launch_segments_copy(const Segment* segs, int count, hipStream_t stream);
 
+// Global-norm gradient clipping (gradclip.hip): the sum of squares of a list of dense
+// tensors of one dtype (`elem_bytes` 4: fp32, 2: bf16) in fp64, and the in-place multiply by
+// min(1, max_norm / (sqrt(sumsq) + eps)) that reads `sumsq` on the device.  One block per
+// chunk of a tensor; up to kGradClipTensors tensors per launch.  `partials` holds
+// grad_clip_blocks() doubles; entries with numel <= 0 are skipped.
+struct GradSpan {
+  void* ptr;
+  int64_t numel;
+};
+constexpr int kGradClipThreads = 256;
+constexpr int kGradClipTensors = 192;
+constexpr int64_t kGradClipChunkF32 = 8192;
+constexpr int64_t kGradClipChunkBF16 = 16384;
+int64_t grad_clip_blocks(const GradSpan* spans, int count, int elem_bytes);
+void launch_grad_sumsq(const GradSpan* spans, int count, int elem_bytes, double* partials,
+                       double* out, hipStream_t stream);
+void launch_grad_scale(const GradSpan* spans, int count, int elem_bytes, const double* sumsq,
+                       double max_norm, double eps, hipStream_t stream);
+
 // Winograd F(2x2,3x3) convolution (3x3, stride 1, pad 1, fp32 NCHW) on f32 MFMA.
 // Transformed weights: U[Rp][Op][16], Rp = wino_pad_reduction(R), Op = wino_pad_output(O).
 // flip = false: w is [O][R][3][3] (forward).  flip = true: w is [R][O][3][3] and the

@@ -107,6 +107,16 @@ class DistributedGPipe:
         self.stage.backward(losses)
         self._outputs = []
 
+    def grad_norm(self, norm_type: float = 2.0) -> Tensor:
+        """The gradient norm over every rank's partition (``PipelineStage.grad_norm``)."""
+        return self.stage.grad_norm(norm_type)
+
+    def clip_grad_norm_(self, max_norm: float, norm_type: float = 2.0,
+                        error_if_nonfinite: bool = False) -> Tensor:
+        """Clip the whole pipeline's gradient norm; every rank calls it after ``backward``
+        (``PipelineStage.clip_grad_norm_``)."""
+        return self.stage.clip_grad_norm_(max_norm, norm_type, error_if_nonfinite)
+
 
 class DistributedGPipeDataLoader:
     """Stage-aware loader: rank 0 yields ``(data, None)`` and ships the target to the

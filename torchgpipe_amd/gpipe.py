@@ -26,6 +26,7 @@ from torch import Tensor, nn
 
 from torchgpipe_amd import microbatch
 from torchgpipe_amd.batchnorm import DeferredBatchNorm, set_micro_batches
+from torchgpipe_amd.ops import gradclip
 from torchgpipe_amd.ops.conv import new_step as wino_new_step
 from torchgpipe_amd.ops.dropout import convert_dropout
 from torchgpipe_amd.ops.fusion import relink
@@ -358,6 +359,20 @@ class GPipe(nn.Module):
                     output = joined if isinstance(output, Tensor) else \
                         (tuple(joined) if isinstance(joined, tuple) else (joined,))
         return output
+
+    def grad_norm(self, norm_type: float = 2.0) -> Tensor:
+        """The ``norm_type`` norm of all partitions' gradients (nothing is modified)."""
+        return gradclip.grad_norm(self.parameters(), norm_type)
+
+    def clip_grad_norm_(self, max_norm: float, norm_type: float = 2.0,
+                        error_if_nonfinite: bool = False) -> Tensor:
+        """Clip the global gradient norm over all partitions in place; returns the norm.
+
+        ``ops.gradclip.clip_grad_norm_`` on ``self.parameters()``: per-device sums of
+        squares on the native kernels, combined on the first device without a host wait.
+        """
+        return gradclip.clip_grad_norm_(self.parameters(), max_norm, norm_type,
+                                        error_if_nonfinite)
 
     def __getstate__(self) -> Any:
         state = self.__dict__.copy()

@@ -5,9 +5,10 @@
 * :mod:`.dropout` — Philox dropout with explicit (seed, offset)
 * :mod:`.philox` — bit-exact CPU reference of the Philox stream
 * :mod:`.misc` — spin kernel (race tests), multi-tensor pack/unpack
+* :mod:`.gradclip` — global-norm gradient clipping (fp64 sum of squares, in-place scale)
 """
-from torchgpipe_amd.ops import _ext
+from torchgpipe_amd.ops import _ext, gradclip
 
 available = _ext.available
 
-__all__ = ['available']
+__all__ = ['available', 'gradclip']

@@ -72,6 +72,9 @@ class StepGraph:
         optimizer: stepped inside the graph when given (its update is captured too).
         warmup: eager steps before the capture (allocator pools, autotuned convolution
             plans, optimizer state, lazily initialised libraries).
+        max_grad_norm: when set, the global gradient norm is clipped to it between the
+            backward and the optimizer step (``stage.clip_grad_norm_``).  The clip stays on
+            the device, so it is captured and replayed; the bound is a captured constant.
 
     ``step(input, target)`` returns the step's loss tensor, which the next replay
     overwrites.  On a CPU stage every step runs eagerly (there is nothing to capture).
@@ -79,7 +82,7 @@ class StepGraph:
 
     def __init__(self, stage: PipelineStage, loss_fn: Callable[[Tensor, Tensor], Tensor],
                  optimizer: Optional[torch.optim.Optimizer] = None, *,
-                 warmup: int = 2) -> None:
+                 warmup: int = 2, max_grad_norm: Optional[float] = None) -> None:
         if stage.world != 1:
             raise ValueError('StepGraph captures one-rank stages only (the graph cannot '
                              'hold point-to-point transfers)')
@@ -94,6 +97,7 @@ class StepGraph:
         self.loss_fn = loss_fn
         self.optimizer = optimizer
         self.warmup = warmup
+        self.max_grad_norm = max_grad_norm
         self._warm = 0
         self._graph: Optional[torch.cuda.CUDAGraph] = None
         self._input: Optional[Tensor] = None
@@ -125,6 +129,8 @@ class StepGraph:
     def _eager(self, input: Tensor, target: Tensor) -> Tensor:
         loss = self.stage.train_step(input, target, self.loss_fn)
         assert loss is not None
+        if self.max_grad_norm is not None:
+            self.stage.clip_grad_norm_(self.max_grad_norm)
         if self.optimizer is not None:
             self.optimizer.step()
         return loss

@@ -30,6 +30,7 @@ output tensors + skips stashed for other ranks, so checkpointing
 from collections import OrderedDict
 import contextlib
 import datetime
+import math
 import threading
 import time
 from typing import (Any, Callable, Dict, FrozenSet, Hashable, List, Optional, Sequence, Tuple,
@@ -44,6 +45,7 @@ from torchgpipe_amd.batchnorm import DeferredBatchNorm, set_micro_batches
 from torchgpipe_amd.checkpoint import Checkpointing
 from torchgpipe_amd.gpipe import check_balance, partition_layers, verify_module
 from torchgpipe_amd.microbatch import Batch
+from torchgpipe_amd.ops import gradclip
 from torchgpipe_amd.ops.conv import new_step as wino_new_step
 from torchgpipe_amd.ops.conv import hold_cache, refresh_step_caches, size_cache_budget
 from torchgpipe_amd.ops.dropout import convert_dropout
@@ -403,6 +405,8 @@ class PipelineStage:
             else:
                 ctrl_group = dist.new_group(ranks=self.ranks, backend='gloo', **group_kwargs)
         self.ctrl_group = ctrl_group
+        self._distributed = distributed  # real peers (not a stand-in transport)
+        self._norm_host: Optional[Tensor] = None  # clip_grad_norm_'s pinned scalar
         self.p2p = transport if transport is not None else \
             P2P(device, group=group, ctrl_group=ctrl_group, pack=pack,
                 link_groups=self._make_links(links, group_kwargs) if distributed else None,
@@ -1395,3 +1399,75 @@ class PipelineStage:
         self.backward(losses)
         with torch.no_grad():
             return torch.stack([l.detach() for l in losses]).sum()
+
+    # -- gradient clipping ------------------------------------------------------------------
+
+    def _grad_power_sum(self, grads: List[Tensor], norm_type: float) -> Tuple[Tensor, bool]:
+        """The pipeline-wide ``ops.gradclip.grad_power_sum`` on this stage's device, and
+        whether any rank holds an fp64 gradient (the dtype of the returned norm)."""
+        local = gradclip.grad_power_sum(grads, norm_type, self.device)
+        wide = gradclip.result_dtype(grads) == torch.float64
+        if self.world == 1 or not self._distributed:
+            return local, wide
+        if self._norm_host is None:
+            self._norm_host = torch.zeros(2, dtype=torch.float64,
+                                          pin_memory=self.device.type == 'cuda')
+        host = self._norm_host
+        host[1] = float(wide)
+        host[:1].copy_(local.reshape(1), non_blocking=True)
+        if self.device.type == 'cuda':
+            # the one host wait of the call: 8 bytes, device to pinned memory
+            torch.cuda.current_stream(self.device).synchronize()
+        # sums add up and flags count; for the inf norm both take the largest
+        op = dist.ReduceOp.MAX if math.isinf(norm_type) else dist.ReduceOp.SUM
+        _wait(dist.all_reduce(host, op=op, group=self.ctrl_group, async_op=True),
+              self.p2p.timeout, 'gradient-norm all-reduce')
+        wide = bool(host[1] > 0)
+        return host[0].to(self.device, non_blocking=True), wide
+
+    def grad_norm(self, norm_type: float = 2.0) -> Tensor:
+        """The ``norm_type`` norm of the whole pipeline's gradients; modifies nothing.
+
+        Collective like :meth:`clip_grad_norm_` (see there): every rank calls it and every
+        rank gets the same value.
+        """
+        with torch.no_grad():
+            grads = gradclip.gradients(self.parameters())
+            total, wide = self._grad_power_sum(grads, float(norm_type))
+            norm = gradclip.norm_of(total, norm_type)
+            return norm.to(torch.float64 if wide else torch.float32)
+
+    def clip_grad_norm_(self, max_norm: float, norm_type: float = 2.0,
+                        error_if_nonfinite: bool = False) -> Tensor:
+        """Clip the gradient norm of the *whole pipeline* in place; returns that norm.
+
+        Call it after ``backward()`` / ``train_step()`` (the deferred weight gradients are
+        flushed by then) and before the optimizer step, on every rank -- also on one whose
+        partition has no parameters.  ``torch.nn.utils.clip_grad_norm_`` on
+        ``stage.parameters()`` would clip each partition to its own norm instead.
+
+        With one rank the call stays on the device: the scale kernel reads the sum of squares
+        there, nothing waits on the host, and the call may be captured in a graph
+        (``StepGraph(max_grad_norm=...)``).  With more ranks the local fp64 sum goes to a
+        pinned host scalar (the one 8-byte device-to-host wait), is all-reduced over the
+        stage's gloo ``ctrl_group`` under the stage's ``timeout`` (a dead peer raises
+        ``PipelineTimeout``) and returns to the device scalar the kernel reads.  The norm is
+        deliberately not all-reduced on the device: that would need an N-rank RCCL
+        communicator and stream next to the per-link ones the stream census counts.
+
+        On a stand-in ``transport`` (loopback emulation of the other ranks) there is no peer
+        to ask: the norm covers the local partition only.
+
+        Returns the norm before clipping as a 0-dim tensor on the stage's device: fp32, or
+        fp64 when any rank's gradients are fp64.  ``error_if_nonfinite=True`` reads it on
+        the host and raises ``RuntimeError`` in PyTorch's words.
+        """
+        max_norm, norm_type = float(max_norm), float(norm_type)
+        with torch.no_grad():
+            grads = gradclip.gradients(self.parameters())
+            total, wide = self._grad_power_sum(grads, norm_type)
+            norm = gradclip.norm_of(total, norm_type)
+            if error_if_nonfinite:
+                gradclip.check_finite(norm, norm_type)
+            gradclip.scale_by_norm_(grads, total, max_norm, norm_type)
+            return norm.to(torch.float64 if wide else torch.float32)
