@@ -92,7 +92,8 @@ def run_stage(args: argparse.Namespace, k: int, dev: torch.device) -> Dict[str, 
     lanes = {'auto': auto, 'on': True, 'off': False}[args.lanes]
     # placeholder transport until the stage knows its skip routes
     sizes = [len(c) for c in torch.empty(args.batch, 0).chunk(args.chunks)]
-    transport = LoopbackP2P(dev, acts, atomic, {}, sizes)
+    wire_dtype = {'none': None, 'bf16': torch.bfloat16}[args.wire_dtype]
+    transport = LoopbackP2P(dev, acts, atomic, {}, sizes, wire_dtype=wire_dtype)
     # (as bench.py: forward and recompute lanes for U-Net, and for ResNet-101 at pipeline-1
     # only; AmoebaNet runs its cells on several streams instead)
     recompute_lane = lanes
@@ -163,7 +164,7 @@ def run_stage(args: argparse.Namespace, k: int, dev: torch.device) -> Dict[str, 
             f.write(prof.key_averages().table(sort_by='self_cpu_time_total', row_limit=60,
                                               max_name_column_width=70))
     row = {'stage': k, 'layers': [lo, hi], 'graph_cells': args.graph_cells,
-           'backward_thread': args.backward_thread,
+           'backward_thread': args.backward_thread, 'wire_dtype': args.wire_dtype,
            'graph_phase': stage.graph_phase, 'lanes': lanes,
            'host_ms': round(host_ms, 2), 'wall_ms': round(wall_ms, 2),
            'device_ms': round(dev_ms, 2), 'host_share': round(host_ms / dev_ms, 3),
@@ -205,6 +206,10 @@ def main() -> None:
                    help='forward / recompute lanes (auto: on for U-Net, as bench.py)')
     p.add_argument('--cell-streams', type=int, default=3,
                    help='AmoebaNet: streams per cell (0: one stream; bench.py: 3)')
+    p.add_argument('--wire-dtype', choices=['none', 'bf16'], default='none',
+                   help='bf16: the stage also encodes what it sends and decodes what it '
+                        'receives (LoopbackP2P(wire_dtype=torch.bfloat16)); sent_bytes stay '
+                        'the logical fp32 sizes')
     p.add_argument('--warmup', type=int, default=3)
     p.add_argument('--steps', type=int, default=2)
     p.add_argument('--out', default=None)

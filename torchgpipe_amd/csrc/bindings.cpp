@@ -148,6 +148,60 @@ void copy_segments(at::TensorList srcs, at::TensorList dsts) {
   }
 }
 
+// copy_segments with a mode per segment (kernels.h WireMode): 0 copies bytes, 1 rounds an
+// fp32 source into a destination of 2 bytes per element, 2 widens such a source into an
+// fp32 destination.  The bf16 side may be a byte view (a slice of a wire buffer).
+void wire_segments(at::TensorList srcs, at::TensorList dsts, at::IntArrayRef modes) {
+  TORCH_CHECK(srcs.size() == dsts.size() && srcs.size() == modes.size(),
+              "srcs, dsts and modes must pair up");
+  if (srcs.empty()) return;
+  const auto device = srcs[0].device();
+  TORCH_CHECK(device.is_cuda(), "wire_segments runs on the GPU");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  std::vector<WireSegment> segs;
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    const at::Tensor& s = srcs[i];
+    const at::Tensor& d = dsts[i];
+    TORCH_CHECK(s.is_contiguous() && d.is_contiguous(), "segments must be contiguous");
+    TORCH_CHECK(s.device() == device && d.device() == device,
+                "segments must live on one device");
+    const int64_t sbytes = s.numel() * s.element_size();
+    const int64_t dbytes = d.numel() * d.element_size();
+    const auto sp = reinterpret_cast<uintptr_t>(s.data_ptr());
+    const auto dp = reinterpret_cast<uintptr_t>(d.data_ptr());
+    int64_t count = 0;
+    switch (modes[i]) {
+      case kWireCopy:
+        TORCH_CHECK(sbytes == dbytes, "segment ", i, ": size mismatch");
+        count = sbytes;
+        break;
+      case kWireEncode:
+        TORCH_CHECK(s.scalar_type() == at::kFloat, "segment ", i, ": encode takes float32");
+        TORCH_CHECK(dbytes == 2 * s.numel(), "segment ", i,
+                    ": the destination of an encode holds 2 bytes per element");
+        TORCH_CHECK(dp % 2 == 0, "segment ", i, ": bf16 destination must be 2-byte aligned");
+        count = s.numel();
+        break;
+      case kWireDecode:
+        TORCH_CHECK(d.scalar_type() == at::kFloat, "segment ", i, ": decode writes float32");
+        TORCH_CHECK(sbytes == 2 * d.numel(), "segment ", i,
+                    ": the source of a decode holds 2 bytes per element");
+        TORCH_CHECK(sp % 2 == 0, "segment ", i, ": bf16 source must be 2-byte aligned");
+        count = d.numel();
+        break;
+      default:
+        TORCH_CHECK(false, "segment ", i, ": unknown wire mode ", modes[i]);
+    }
+    if (count == 0) continue;  // empty tensors launch nothing
+    segs.push_back({s.data_ptr(), d.data_ptr(), count, static_cast<int>(modes[i])});
+  }
+  const hipStream_t stream = at::hip::getCurrentHIPStream(device.index()).stream();
+  for (size_t i = 0; i < segs.size(); i += kMaxSegments) {
+    const int count = static_cast<int>(std::min<size_t>(kMaxSegments, segs.size() - i));
+    launch_wire_segments(segs.data() + i, count, stream);
+  }
+}
+
 // The dense tensors of one dtype (fp32 or bf16) on one GPU that the gradient-clipping
 // kernels take, as spans; empty tensors are left out.  Returns the element size.
 int grad_spans(at::TensorList grads, const char* op, std::vector<GradSpan>& spans) {
@@ -559,6 +613,8 @@ TORCH_LIBRARY(tgpipe, m) {
   m.def("philox_uniform(int n, int seed, int offset, Device device, Tensor? rng=None) -> Tensor");
   m.def("spin(int ns, Device device) -> ()");
   m.def("copy_segments(Tensor[] srcs, Tensor(a!)[] dsts) -> ()");
+  // copy_segments with a mode per segment: 0 copy, 1 fp32 -> bf16 (RNE), 2 bf16 -> fp32
+  m.def("wire_segments(Tensor[] srcs, Tensor(a!)[] dsts, int[] modes) -> ()");
   // global-norm gradient clipping: fp64 sum of squares [1], in-place scale reading it
   m.def("grad_sumsq(Tensor[] grads) -> Tensor");
   m.def("grad_scale_(Tensor(a!)[] grads, Tensor sumsq, float max_norm, float eps) -> ()");
@@ -594,6 +650,7 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("dna_backward", &tgpipe::dna_backward);
   m.impl("dropout", &tgpipe::dropout);
   m.impl("copy_segments", &tgpipe::copy_segments);
+  m.impl("wire_segments", &tgpipe::wire_segments);
   m.impl("grad_scale_", &tgpipe::grad_scale_);
   m.impl("wino_weight", &tgpipe::wino_weight);
   m.impl("wino_conv", &tgpipe::wino_conv);

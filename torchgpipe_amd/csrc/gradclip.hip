@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_round.h"
 #include "kernels.h"
 
 namespace tgpipe {
@@ -121,14 +122,6 @@ __device__ __forceinline__ float widen<float>(const uint32_t (&w)[4], int k) {
 template <>
 __device__ __forceinline__ float widen<bf16_bits>(const uint32_t (&w)[4], int k) {
   return __uint_as_float(k & 1 ? w[k >> 1] & 0xffff0000u : w[k >> 1] << 16);
-}
-
-// Round to nearest even; NaN stays a (quiet) NaN.
-__device__ __forceinline__ uint32_t to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
 }
 
 // Sum over the block in a fixed order; the result is valid on thread 0.

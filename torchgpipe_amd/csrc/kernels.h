@@ -63,6 +63,19 @@ struct Segment {
 constexpr int kMaxSegments = 16;
 void launch_segments_copy(const Segment* segs, int count, hipStream_t stream);
 
+// The same with a precision change per segment (wire.hip: the bf16 wire format of
+// inter-stage messages).  `count` is bytes for kWireCopy and elements for kWireEncode
+// (src fp32 -> dst bf16, round to nearest even) / kWireDecode (src bf16 -> dst fp32, exact).
+// Up to kMaxSegments segments per launch.
+enum WireMode : int { kWireCopy = 0, kWireEncode = 1, kWireDecode = 2 };
+struct WireSegment {
+  const void* src;
+  void* dst;
+  int64_t count;
+  int mode;
+};
+void launch_wire_segments(const WireSegment* segs, int count, hipStream_t stream);
+
 // Global-norm gradient clipping (gradclip.hip): the sum of squares of a list of dense
 // tensors of one dtype (`elem_bytes` 4: fp32, 2: bf16) in fp64, and the in-place multiply by
 // min(1, max_norm / (sqrt(sumsq) + eps)) that reads `sumsq` on the device.  One block per

@@ -14,7 +14,9 @@ API parity with ``torchgpipe/distributed/gpipe.py:26-275``:
 Differences (all improvements): tensors go GPU→GPU over RCCL instead of
 CPU-staged RPC; activation checkpointing (``checkpoint=``), skip connections
 and deferred BatchNorm work; ``workers`` (rank → name) is only used for
-naming since ranks address each other through ``torch.distributed``.
+naming since ranks address each other through ``torch.distributed``;
+``wire_dtype=torch.bfloat16`` sends float32 activations and gradients as bfloat16
+(``PipelineStage``'s ``wire_dtype`` / ``wire_kinds``).
 """
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
@@ -55,7 +57,9 @@ class DistributedGPipe:
                  balance: Optional[Iterable[int]] = None, microbatch_chunks: int = chunks, *,
                  device: Optional[torch.device] = None, deferred_batch_norm: bool = False,
                  checkpoint: str = 'never', group: Optional[dist.ProcessGroup] = None,
-                 timeout: Optional[float] = None) -> None:
+                 timeout: Optional[float] = None,
+                 wire_dtype: Optional[torch.dtype] = None,
+                 wire_kinds: Sequence[str] = ('act', 'skip', 'gact', 'gskip')) -> None:
         microbatch_chunks = int(microbatch_chunks)
         if balance is None:
             raise ValueError(recommend_auto_balance('balance is required'))
@@ -76,7 +80,8 @@ class DistributedGPipe:
         self.device = device if device is not None else torch.device('cpu')
         self.stage = PipelineStage(module, balance, rank=rank, device=self.device,
                                    chunks=microbatch_chunks, checkpoint=checkpoint, group=group,
-                                   deferred_batch_norm=deferred_batch_norm, timeout=timeout)
+                                   deferred_batch_norm=deferred_batch_norm, timeout=timeout,
+                                   wire_dtype=wire_dtype, wire_kinds=wire_kinds)
         self.module = self.stage.partition
         self._outputs: List[TensorOrTensors] = []
 

@@ -12,12 +12,18 @@ pipeline's per-stage costs with zero transfer time (``benchmarks/stage_harness.p
 
 Receive buffers are made once per message key and reused (as ``P2P``'s persistent
 receives are), so captured cells replay on them in place.
+
+With ``wire_dtype`` the stage also pays what a reduced-precision wire costs it: every
+message it is sent is encoded into a wire buffer first (then dropped), and every message it
+receives is decoded from a wire buffer kept per key into the buffers it hands out -- the two
+kernels of ``ops.misc.pack_wire`` / ``unpack_wire`` per message, as on a real link.
 """
 from typing import Dict, Hashable, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
+from torchgpipe_amd.ops import misc
 from torchgpipe_amd.parallel.p2p import Message, TensorMeta
 
 __all__ = ['LoopbackP2P']
@@ -35,13 +41,21 @@ class LoopbackP2P:
         sizes: the batch size of each micro-batch when they differ (a mini-batch that does
             not split evenly: the last micro-batch is smaller); the templates are trimmed
             to it along dim 0.
+        wire_dtype: ``torch.bfloat16``: float32 tensors pass through the bf16 wire format
+            (``P2P``'s ``wire_dtype``), so what the stage receives is the template rounded
+            through bfloat16; ``None``: as they are.
     """
 
     stage_host = False
 
     def __init__(self, device: torch.device, acts: Sequence[Tensor], acts_atomic: bool,
                  skips: Dict[int, List[Tensor]],
-                 sizes: Optional[Sequence[int]] = None) -> None:
+                 sizes: Optional[Sequence[int]] = None,
+                 wire_dtype: Optional[torch.dtype] = None) -> None:
+        if wire_dtype is not None and wire_dtype != torch.bfloat16:
+            raise ValueError(f'wire_dtype must be None or torch.bfloat16, not {wire_dtype!r}')
+        self.wire_dtype = wire_dtype
+        self._wire: Dict[Hashable, Tensor] = {}  # the wire buffer of each received key
         self.device = device
         self.sizes = list(sizes) if sizes is not None else None
         self.acts = [t.detach() for t in acts]
@@ -61,6 +75,15 @@ class LoopbackP2P:
              atomic: bool = False, cache: bool = True) -> None:
         kind, i, src, _ = self._fields(key)
         self._sent[(kind, i, dst)] = [TensorMeta.of(t) for t in tensors]
+        if self._wired(tensors):
+            buf = torch.empty(max(misc.wire_nbytes(tensors, self.wire_dtype), 16),
+                              dtype=torch.uint8, device=tensors[0].device)
+            misc.pack_wire([t.detach() for t in tensors], buf, self.wire_dtype)
+
+    def _wired(self, tensors: Sequence[Tensor]) -> bool:
+        """Whether a message of these tensors travels in the wire format (``P2P``'s rule)."""
+        return self.wire_dtype is not None and \
+            any(t.dtype == torch.float32 for t in tensors)
 
     def _source(self, kind: str, i: int, src: int, me: int) -> List[Tuple[Tensor, bool]]:
         """(template tensor, requires_grad) of every tensor of the message."""
@@ -94,6 +117,12 @@ class LoopbackP2P:
                     b = t.to(self.device).clone()
                 bufs.append(b)
             self._bufs[key] = bufs
+            if self._wired(bufs):
+                wire = torch.empty(max(misc.wire_nbytes(bufs, self.wire_dtype), 16),
+                                   dtype=torch.uint8, device=self.device)
+                self._wire[key] = misc.pack_wire(bufs, wire, self.wire_dtype)
+        if key in self._wire:  # the receiver's decode, every step
+            misc.unpack_wire(self._wire[key], bufs, self.wire_dtype)
         return Message([], list(bufs), None, metas, atomic)
 
     def send_control(self, payload: Tensor, dst: int) -> None:
@@ -107,6 +136,7 @@ class LoopbackP2P:
 
     def forget(self) -> None:
         self._bufs.clear()
+        self._wire.clear()
 
     def flush(self) -> None:
         pass

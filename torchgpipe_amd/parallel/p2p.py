@@ -15,6 +15,13 @@ skip tensors bound for the same rank) is packed into one flat byte buffer by
 the HIP segment-copy kernel (one RCCL send instead of several) and unpacked on
 the receiver as zero-copy views into the received buffer.
 
+Wire format.  With ``wire_dtype=torch.bfloat16`` the pipeline's own messages (kinds
+``wire_kinds``) that hold a float32 tensor travel as one flat *wire buffer* -- single-tensor
+messages too -- in which every float32 tensor is stored as bfloat16 (``ops.misc.pack_wire``:
+the rounding is part of the pack launch) and every other tensor verbatim.  Host staging,
+striping and the recorded sizes see wire bytes; the receiver decodes at ``wait()`` into
+tensors of the sender's dtype and shape, which the metadata keeps describing.
+
 Metadata.  Receivers must allocate buffers before posting a receive.
 Shapes are exchanged once per (step signature, micro-batch, link, direction)
 over a CPU ``gloo`` control group — so no GPU→host synchronisation is ever
@@ -72,10 +79,35 @@ class TensorMeta:
         return n * torch.empty((), dtype=self.dtype).element_size()
 
 
-def encode_metas(metas: Sequence[TensorMeta], atomic: bool = False) -> Tensor:
+# The message kinds a wire format may apply to, in the bit order of the header's kinds word.
+WIRE_KINDS = ('act', 'skip', 'gact', 'gskip')
+
+# The sender's wire setting as the header carries it: (wire dtype code + 1, or 0 for none;
+# bit mask of its wire kinds).
+WireSetting = Tuple[int, int]
+
+
+def wire_setting(wire_dtype: Optional[torch.dtype], wire_kinds: Sequence[str]) -> WireSetting:
+    if wire_dtype is None:
+        return (0, 0)
+    return (_DTYPE_CODE[wire_dtype] + 1,
+            sum(1 << WIRE_KINDS.index(k) for k in set(wire_kinds)))
+
+
+def describe_wire(setting: WireSetting) -> str:
+    code, mask = setting
+    if code == 0:
+        return 'wire_dtype=None'
+    kinds = tuple(k for b, k in enumerate(WIRE_KINDS) if mask >> b & 1)
+    return f'wire_dtype={_DTYPES[code - 1]}, wire_kinds={kinds}'
+
+
+def encode_metas(metas: Sequence[TensorMeta], atomic: bool = False,
+                 wire: WireSetting = (0, 0)) -> Tensor:
     words: List[int] = [len(metas), int(atomic)]
     for m in metas:
         words += [_DTYPE_CODE[m.dtype], int(m.requires_grad), len(m.shape), *m.shape]
+    words += list(wire)  # after the tensors: the sender's wire setting
     if len(words) > _HEADER_LEN:
         raise ValueError('message metadata too large')
     header = torch.zeros(_HEADER_LEN, dtype=torch.int64)
@@ -83,7 +115,7 @@ def encode_metas(metas: Sequence[TensorMeta], atomic: bool = False) -> Tensor:
     return header
 
 
-def decode_metas(header: Tensor) -> Tuple[List[TensorMeta], bool]:
+def decode_header(header: Tensor) -> Tuple[List[TensorMeta], bool, WireSetting]:
     words = header.tolist()
     count, atomic, pos = words[0], bool(words[1]), 2
     metas: List[TensorMeta] = []
@@ -94,6 +126,11 @@ def decode_metas(header: Tensor) -> Tuple[List[TensorMeta], bool]:
         shape = tuple(words[pos + 3:pos + 3 + ndim])
         pos += 3 + ndim
         metas.append(TensorMeta(shape, dtype, grad))
+    return metas, atomic, (words[pos], words[pos + 1])
+
+
+def decode_metas(header: Tensor) -> Tuple[List[TensorMeta], bool]:
+    metas, atomic, _ = decode_header(header)
     return metas, atomic
 
 
@@ -134,13 +171,15 @@ class Message:
     """Handle of a posted receive: ``wait()`` returns the received tensors."""
 
     __slots__ = ('_works', '_tensors', '_buffer', '_metas', 'atomic', '_device', '_timeout',
-                 '_what', '_dest')
+                 '_what', '_dest', '_wire')
 
     def __init__(self, works: List[object], tensors: Optional[List[Tensor]],
                  buffer: Optional[Tensor], metas: List[TensorMeta], atomic: bool,
                  device: Optional[torch.device] = None,
                  timeout: Optional[datetime.timedelta] = None, what: str = '',
-                 dest: Optional[List[Tensor]] = None) -> None:
+                 dest: Optional[List[Tensor]] = None,
+                 wire: Optional[Tuple[Optional[torch.dtype], List[List[int]], torch.device,
+                                      Optional[List[Tensor]]]] = None) -> None:
         self._works = works
         self._timeout = timeout
         self._what = what
@@ -153,6 +192,10 @@ class Message:
         # (persistent device buffers, same layout as the host ones) when given.
         self._device = device
         self._dest = dest
+        # Wire-format receive: ``tensors`` are the flat wire buffers, one per group of
+        # ``metas`` indices; wait() decodes them on the current stream of the device into
+        # tensors as ``metas`` describes (the given persistent ones, else fresh).
+        self._wire = wire
 
     def wait(self) -> List[Tensor]:
         """Wait (stream-ordered on GPUs) and return detached leaf tensors.
@@ -179,6 +222,15 @@ class Message:
                 if self._buffer is not None:
                     self._buffer = self._buffer.to(self._device, non_blocking=True)
             self._device = None
+        if self._wire is not None:
+            wire_dtype, groups, device, keep = self._wire
+            assert self._tensors is not None
+            outs = keep if keep is not None else \
+                [torch.empty(m.shape, dtype=m.dtype, device=device) for m in self._metas]
+            for buf, group in zip(self._tensors, groups):
+                misc.unpack_wire(buf, [outs[k] for k in group], wire_dtype)
+            self._tensors = list(outs)
+            self._wire = None
         if self._tensors is None:
             assert self._buffer is not None
             views: List[Tensor] = []
@@ -230,13 +282,31 @@ class P2P:
         ctrl_group: ``gloo`` group for metadata (may equal ``group`` on CPU).
         timeout: bound (seconds) of every host-blocking wait; ``None`` = the
             process group's own timeout.
+        wire_dtype: ``torch.bfloat16``: the float32 tensors of the pipeline's messages
+            travel as bfloat16 (rounded to nearest even by the sender's pack kernel, widened
+            by the receiver's; ``ops.misc.pack_wire``).  Tensors of other dtypes, and
+            messages that are not of ``wire_kinds`` (targets, control payloads, one-shot
+            keys), travel as ever.  Receivers hand out tensors of the sender's dtype and
+            shape.  ``None`` (default): every byte as is.  Both ends of a link must agree:
+            the first exchange of each message checks it.
+        wire_kinds: the message kinds ``wire_dtype`` applies to.
     """
 
     def __init__(self, device: torch.device, group: Optional[dist.ProcessGroup] = None,
                  ctrl_group: Optional[dist.ProcessGroup] = None,
                  pack: bool = True,
                  link_groups: Optional[Dict[int, dist.ProcessGroup]] = None,
-                 timeout: Optional[float] = None) -> None:
+                 timeout: Optional[float] = None,
+                 wire_dtype: Optional[torch.dtype] = None,
+                 wire_kinds: Sequence[str] = WIRE_KINDS) -> None:
+        if wire_dtype is not None and wire_dtype != torch.bfloat16:
+            raise ValueError(f'wire_dtype must be None or torch.bfloat16, not {wire_dtype!r}')
+        unknown = [k for k in wire_kinds if k not in WIRE_KINDS]
+        if unknown:
+            raise ValueError(f'wire_kinds must be among {WIRE_KINDS}, not {unknown}')
+        self.wire_dtype = wire_dtype
+        self.wire_kinds = frozenset(wire_kinds)
+        self._wire_setting = wire_setting(wire_dtype, wire_kinds)
         self.device = device
         self.timeout = None if timeout is None else datetime.timedelta(seconds=timeout)
         self.group = group
@@ -276,14 +346,36 @@ class P2P:
     def _send_meta(self, metas: Sequence[TensorMeta], atomic: bool, dst: int) -> None:
         # Non-blocking: a blocking gloo send could wait on a receiver that is
         # itself waiting for an upstream rank.
-        self._pending_meta.append(dist.isend(encode_metas(metas, atomic), dst,
-                                             group=self.ctrl_group))
+        self._pending_meta.append(dist.isend(encode_metas(metas, atomic, self._wire_setting),
+                                             dst, group=self.ctrl_group))
 
     def _recv_meta(self, src: int, key: Hashable) -> Tuple[List[TensorMeta], bool]:
         header = torch.empty(_HEADER_LEN, dtype=torch.int64)
         _wait(dist.irecv(header, src, group=self.ctrl_group), self.timeout,
               f'metadata of message {key!r} from rank {src}')
-        return decode_metas(header)
+        metas, atomic, wire = decode_header(header)
+        if wire != self._wire_setting and message_kind(key) in WIRE_KINDS:
+            # never reinterpret bytes: the sizes on the link would differ (or worse, agree)
+            raise RuntimeError(
+                f'message {key!r} from rank {src}: the sender runs with {describe_wire(wire)} '
+                f'but this rank with {describe_wire(self._wire_setting)}; every rank of a '
+                f'pipeline must be given the same wire format')
+        return metas, atomic
+
+    def _wire_groups(self, key: Hashable,
+                     metas: Sequence[TensorMeta]) -> Optional[List[List[int]]]:
+        """How message ``key`` travels in the wire format: the tensor indices of each flat
+        wire buffer (one for all, or with ``pack=False`` one per tensor); ``None`` when it
+        travels as is (no wire format, another kind of message, or no float32 tensor)."""
+        if self.wire_dtype is None or message_kind(key) not in self.wire_kinds or \
+                not any(m.dtype == torch.float32 for m in metas):
+            return None
+        if self.pack or len(metas) == 1:
+            return [list(range(len(metas)))]
+        return [[k] for k in range(len(metas))]
+
+    def _wire_nbytes(self, metas: Sequence[TensorMeta]) -> int:
+        return max(misc.wire_nbytes(metas, self.wire_dtype), 16)
 
     def send_control(self, payload: Tensor, dst: int) -> None:
         """Non-blocking send of a small CPU int64 tensor on the control group."""
@@ -323,6 +415,10 @@ class P2P:
                 f'message {key!r} changed shape/dtype under the same step signature '
                 f'({cached} -> {metas}); the receiver would misinterpret it')
         self._prune()
+        groups = self._wire_groups(key, metas)
+        if groups is not None:
+            self._send_wire(tensors, metas, groups, dst, key)
+            return
         single = len(tensors) == 1
         if self._recording is not None:
             kind = message_kind(key) if single or self.pack else 'unpacked'
@@ -347,6 +443,53 @@ class P2P:
             return
         self._pending_sends.append(dist.isend(buf, dst, group=self._link(dst)))
 
+    def _send_wire(self, tensors: Sequence[Tensor], metas: Sequence[TensorMeta],
+                   groups: List[List[int]], dst: int, key: Hashable) -> None:
+        """Send a message in the wire format: each group of tensors encoded into one flat
+        wire buffer, which is what host staging, striping and the link then see."""
+        whole = len(groups) == 1
+        sizes = [self._wire_nbytes([metas[k] for k in g]) for g in groups]
+        if self._recording is not None:
+            kind = message_kind(key) if whole else 'unpacked'
+            self._recording.append(Send(dst, kind or 'other', sum(sizes)))
+        for group, nbytes in zip(groups, sizes):
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=tensors[group[0]].device)
+            misc.pack_wire([tensors[k].detach() for k in group], buf, self.wire_dtype)
+            if self.stage_host:
+                buf = buf.cpu()
+            if whole and self._striped(self.me, dst, nbytes, key):
+                self._send_pieces(buf, dst)
+                return
+            self._pending_sends.append(dist.isend(buf, dst, group=self._link(dst)))
+
+    def _recv_wire(self, src: int, key: Hashable, metas: List[TensorMeta], atomic: bool,
+                   groups: List[List[int]], persistent: bool) -> Message:
+        """Post the receive of a wire-format message: into flat wire buffers (kept per key
+        when ``persistent``, as are the decoded tensors), decoded at ``wait()``."""
+        where = torch.device('cpu') if self.stage_host else self.device
+        sizes = [self._wire_nbytes([metas[k] for k in g]) for g in groups]
+        keep: Optional[List[Tensor]] = None
+        outs: Optional[List[Tensor]] = None
+        if persistent:
+            kept = self._bufs.get(key)
+            if kept is None:
+                kept = self._bufs[key] = \
+                    [torch.empty(n, dtype=torch.uint8, device=self.device) for n in sizes] + \
+                    [torch.empty(m.shape, dtype=m.dtype, device=self.device) for m in metas]
+            keep, outs = kept[:len(groups)], kept[len(groups):]
+        bufs = ([torch.empty(n, dtype=torch.uint8, device=where) for n in sizes]
+                if keep is None or self.stage_host else list(keep))
+        if len(bufs) == 1 and self._striped(src, self.me, sizes[0], key):
+            works = self._recv_pieces(bufs[0], src)
+        else:
+            works = [dist.irecv(b, src, group=self._link(src)) for b in bufs]
+        return Message(works, bufs, None, metas, atomic,
+                       self.device if self.stage_host else None,
+                       self.timeout if self._host_waits else None,
+                       f'message {key!r} from rank {src}',
+                       keep if self.stage_host else None,
+                       wire=(self.wire_dtype, groups, self.device, outs))
+
     def recv(self, src: int, key: Hashable, cache: bool = True,
              persistent: bool = False) -> Message:
         """Post a receive from ``src``; the returned handle's ``wait()`` yields tensors.
@@ -365,6 +508,9 @@ class P2P:
         metas, atomic = cached
         if not metas:
             return Message([], [], None, metas, atomic)
+        groups = self._wire_groups(key, metas)
+        if groups is not None:
+            return self._recv_wire(src, key, metas, atomic, groups, persistent)
         where = torch.device('cpu') if self.stage_host else self.device
         late = self.device if self.stage_host else None
         timeout = self.timeout if self._host_waits else None

@@ -296,6 +296,15 @@ class PipelineStage:
             recomputed graph (one autograd engine call) instead of through its Checkpoint
             node, whose backward re-enters the engine for the same work (default on; off
             restores the reference's Checkpoint/Recompute choreography exactly).
+        wire_dtype: ``torch.bfloat16``: float32 activations, skips and their gradients cross
+            rank boundaries as bfloat16 -- rounded to nearest even once per crossing by the
+            kernel that packs the message, widened back to float32 on arrival -- which
+            halves the bytes on the links; everything else (other dtypes, targets, control
+            messages) and all arithmetic stay as they are.  Every rank must pass the same
+            value (checked on the first exchange).  ``None`` (default): off.  With a
+            stand-in ``transport`` the transport's own setting applies.
+        wire_kinds: the message kinds ``wire_dtype`` applies to, among ``'act'``, ``'skip'``
+            (forward) and ``'gact'``, ``'gskip'`` (their gradients); default all four.
         backward_thread: issue each micro-batch's backward from a helper thread, so the
             host enqueues the next micro-batch's recomputation (and posts its receives)
             while the autograd engine enqueues this backward: the two host streams of
@@ -323,7 +332,9 @@ class PipelineStage:
                  stripes: Optional[int] = None,
                  stripe_relays: int = 3,
                  backward_thread: bool = False,
-                 direct_backward: bool = True) -> None:
+                 direct_backward: bool = True,
+                 wire_dtype: Optional[torch.dtype] = None,
+                 wire_kinds: Sequence[str] = ('act', 'skip', 'gact', 'gskip')) -> None:
         if chunks <= 0:
             raise ValueError('number of chunks must be positive integer')
         if checkpoint not in ('always', 'except_last', 'never'):
@@ -410,7 +421,7 @@ class PipelineStage:
         self.p2p = transport if transport is not None else \
             P2P(device, group=group, ctrl_group=ctrl_group, pack=pack,
                 link_groups=self._make_links(links, group_kwargs) if distributed else None,
-                timeout=timeout)
+                timeout=timeout, wire_dtype=wire_dtype, wire_kinds=wire_kinds)
 
         self._cells: List[_Cell] = []
         self.overlap_recompute = overlap_recompute
