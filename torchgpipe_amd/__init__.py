@@ -7,6 +7,8 @@ Public API (compatible with ``torchgpipe``):
 * :mod:`torchgpipe_amd.skip` — ``@skippable`` long skip connections
 * :mod:`torchgpipe_amd.balance` — ``balance_by_time`` / ``balance_by_size``
 * :mod:`torchgpipe_amd.batchnorm` — ``DeferredBatchNorm``
+* :mod:`torchgpipe_amd.optim` — ``SGD`` / ``RMSprop`` on one-pass native kernels, with a
+  device-resident learning rate and the gradient clip fused into the update
 * :mod:`torchgpipe_amd.distributed` — multi-process pipeline (one rank per GPU,
   RCCL point-to-point over xGMI): ``DistributedGPipe``,
   ``DistributedGPipeDataLoader``

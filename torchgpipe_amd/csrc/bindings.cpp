@@ -266,6 +266,116 @@ std::vector<int64_t> grad_clip_info() {
   return {kGradClipChunkF32, kGradClipChunkBF16, kGradClipTensors, kGradClipThreads};
 }
 
+// The lists of a fused optimizer step (optim.hip) as spans: `lists[0]` the parameters,
+// `lists[1]` the gradients, the others state tensors; `rows[l]` is list l's pointer slot in
+// OptimSpan.  grad_spans' conditions -- GPU, dense, one device -- with fp32 only, and per
+// position one numel and one memory layout, since the kernels walk storage order.  Empty
+// tensors are left out.
+void optim_spans(const std::vector<at::TensorList>& lists, const std::vector<int>& rows,
+                 const char* op, std::vector<OptimSpan>& spans) {
+  const at::TensorList params = lists[0];
+  for (const at::TensorList& list : lists)
+    TORCH_CHECK(list.size() == params.size(), op, " takes lists of one length");
+  for (size_t i = 0; i < params.size(); ++i) {
+    const at::Tensor& p = params[i];
+    OptimSpan span{};
+    for (size_t l = 0; l < lists.size(); ++l) {
+      const at::Tensor& t = lists[l][i];
+      TORCH_CHECK(t.defined() && t.is_cuda(), op, " takes GPU tensors");
+      TORCH_CHECK(t.layout() == at::kStrided && t.is_non_overlapping_and_dense(), op,
+                  " takes dense tensors");
+      TORCH_CHECK(t.scalar_type() == at::kFloat, op, " takes float32 tensors");
+      TORCH_CHECK(t.device() == params[0].device(), op, " takes tensors of one device");
+      TORCH_CHECK(t.numel() == p.numel(), op, " takes tensors of equal numel per position");
+      TORCH_CHECK(t.strides() == p.strides() || t.numel() <= 1, op,
+                  " takes tensors of one memory layout per position");
+      span.ptr[rows[l]] = t.data_ptr<float>();
+    }
+    span.numel = p.numel();
+    if (span.numel > 0) spans.push_back(span);
+  }
+}
+
+// The device scalars of a step: the fp32 learning rate and the optional fp64 sum of squares.
+const float* optim_lr(const at::Tensor& lr, const at::Device& device, const char* op) {
+  TORCH_CHECK(lr.is_cuda() && lr.device() == device && lr.scalar_type() == at::kFloat &&
+                  lr.numel() == 1,
+              op, ": lr must be a float32 scalar tensor on the parameters' device");
+  return lr.data_ptr<float>();
+}
+
+const double* optim_sumsq(const c10::optional<at::Tensor>& sumsq, const at::Device& device,
+                          const char* op) {
+  if (!sumsq.has_value() || !sumsq->defined()) return nullptr;
+  TORCH_CHECK(sumsq->is_cuda() && sumsq->device() == device &&
+                  sumsq->scalar_type() == at::kDouble && sumsq->numel() >= 1,
+              op, ": sumsq must be a float64 tensor on the parameters' device");
+  return sumsq->data_ptr<double>();
+}
+
+// The custom-op schema's (a!) does not advance the version counter, and ops/conv.py,
+// ops/convbn.py and convbn.cpp key their weight caches on it.
+void bump_versions(at::TensorList tensors) {
+  for (const at::Tensor& t : tensors)
+    if (!t.is_inference()) t.unsafeGetTensorImpl()->bump_version();
+}
+
+void sgd_step_(at::TensorList params, at::TensorList grads, at::TensorList bufs,
+               const at::Tensor& lr, double momentum, double dampening, bool nesterov,
+               double weight_decay, bool first, const c10::optional<at::Tensor>& sumsq,
+               double max_norm, double clip_eps) {
+  TORCH_CHECK(momentum != 0.0 || bufs.empty(), "sgd_step_ takes no buffers without momentum");
+  std::vector<at::TensorList> lists = {params, grads};
+  if (momentum != 0.0) lists.push_back(bufs);
+  std::vector<OptimSpan> spans;
+  optim_spans(lists, {0, 1, 2}, "sgd_step_", spans);
+  if (params.empty()) return;
+  const auto device = params[0].device();
+  const float* lr_ptr = optim_lr(lr, device, "sgd_step_");
+  const double* sumsq_ptr = optim_sumsq(sumsq, device, "sgd_step_");
+  if (spans.empty()) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  launch_sgd_step(spans.data(), static_cast<int>(spans.size()), lr_ptr, momentum, dampening,
+                  nesterov, weight_decay, first, sumsq_ptr, max_norm, clip_eps,
+                  at::hip::getCurrentHIPStream(device.index()).stream());
+  check_launched("sgd_step_");
+  bump_versions(params);
+  if (momentum != 0.0) bump_versions(bufs);
+}
+
+void rmsprop_step_(at::TensorList params, at::TensorList grads, at::TensorList square_avgs,
+                   at::TensorList grad_avgs, at::TensorList bufs, const at::Tensor& lr,
+                   double alpha, double eps, double weight_decay, double momentum, bool centered,
+                   const c10::optional<at::Tensor>& sumsq, double max_norm, double clip_eps) {
+  TORCH_CHECK(centered || grad_avgs.empty(), "rmsprop_step_ takes grad_avgs only when centered");
+  TORCH_CHECK(momentum > 0.0 || bufs.empty(), "rmsprop_step_ takes no buffers without momentum");
+  std::vector<at::TensorList> lists = {params, grads, square_avgs};
+  std::vector<int> rows = {0, 1, 2};
+  if (centered) { lists.push_back(grad_avgs); rows.push_back(3); }
+  if (momentum > 0.0) { lists.push_back(bufs); rows.push_back(4); }
+  std::vector<OptimSpan> spans;
+  optim_spans(lists, rows, "rmsprop_step_", spans);
+  if (params.empty()) return;
+  const auto device = params[0].device();
+  const float* lr_ptr = optim_lr(lr, device, "rmsprop_step_");
+  const double* sumsq_ptr = optim_sumsq(sumsq, device, "rmsprop_step_");
+  if (spans.empty()) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  launch_rmsprop_step(spans.data(), static_cast<int>(spans.size()), lr_ptr, alpha, eps,
+                      weight_decay, momentum, centered, sumsq_ptr, max_norm, clip_eps,
+                      at::hip::getCurrentHIPStream(device.index()).stream());
+  check_launched("rmsprop_step_");
+  bump_versions(params);
+  bump_versions(square_avgs);
+  if (centered) bump_versions(grad_avgs);
+  if (momentum > 0.0) bump_versions(bufs);
+}
+
+// (chunk elements, tensors per launch, threads per block)
+std::vector<int64_t> optim_info() {
+  return {kOptimChunk, kOptimTensors, kOptimThreads};
+}
+
 // `out` (optional): an existing transform of the same shape to overwrite in place (the
 // per-step cache refresh, ops/conv.py) instead of a new tensor plus a copy.
 at::Tensor transform_out(const c10::optional<at::Tensor>& out, at::IntArrayRef shape,
@@ -619,6 +729,16 @@ TORCH_LIBRARY(tgpipe, m) {
   m.def("grad_sumsq(Tensor[] grads) -> Tensor");
   m.def("grad_scale_(Tensor(a!)[] grads, Tensor sumsq, float max_norm, float eps) -> ()");
   m.def("grad_clip_info() -> int[]", &tgpipe::grad_clip_info);
+  // fused optimizer steps: lr is a device fp32 scalar; sumsq (fp64, device) clips in the pass
+  m.def("sgd_step_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] bufs, Tensor lr, "
+        "float momentum, float dampening, bool nesterov, float weight_decay, bool first, "
+        "Tensor? sumsq, float max_norm, float clip_eps) -> ()");
+  m.def("rmsprop_step_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] square_avgs, "
+        "Tensor(c!)[] grad_avgs, Tensor(d!)[] bufs, Tensor lr, float alpha, float eps, "
+        "float weight_decay, float momentum, bool centered, Tensor? sumsq, float max_norm, "
+        "float clip_eps) -> ()");
+  // [chunk elements, tensors per launch, threads per block]
+  m.def("optim_info() -> int[]", &tgpipe::optim_info);
   m.def("wino_weight(Tensor w, bool flip, Tensor? out=None) -> Tensor");
   m.def("wino_wgrad(Tensor x, Tensor dy, int splits=0, int variant=-1, Tensor? into=None) -> Tensor");
   m.def("wino_conv(Tensor x, Tensor u, Tensor? bias, int out_channels, int variant=-1, "
@@ -652,6 +772,8 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("copy_segments", &tgpipe::copy_segments);
   m.impl("wire_segments", &tgpipe::wire_segments);
   m.impl("grad_scale_", &tgpipe::grad_scale_);
+  m.impl("sgd_step_", &tgpipe::sgd_step_);
+  m.impl("rmsprop_step_", &tgpipe::rmsprop_step_);
   m.impl("wino_weight", &tgpipe::wino_weight);
   m.impl("wino_conv", &tgpipe::wino_conv);
   m.impl("wino_wgrad", &tgpipe::wino_wgrad);

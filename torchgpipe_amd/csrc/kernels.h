@@ -95,6 +95,30 @@ void launch_grad_sumsq(const GradSpan* spans, int count, int elem_bytes, double*
 void launch_grad_scale(const GradSpan* spans, int count, int elem_bytes, const double* sumsq,
                        double max_norm, double eps, hipStream_t stream);
 
+// Fused optimizer steps (optim.hip) over lists of dense fp32 tensors: per position a
+// parameter, its gradient and up to three state tensors of the same numel and layout, updated
+// in one pass.  `lr` is a device fp32 scalar.  `sumsq` (optional) is the device fp64 sum of
+// squares of all gradients: when max_norm / (sqrt(sumsq) + clip_eps) is below 1 or NaN every
+// gradient is multiplied by it (in fp32, rounded on its own) as it is loaded; the gradients
+// are never written.  One block per chunk of kOptimChunk elements; up to kOptimTensors
+// tensors per launch; entries with numel <= 0 are skipped.
+constexpr int kOptimThreads = 256;
+constexpr int kOptimTensors = 64;
+constexpr int kOptimStreams = 5;
+constexpr int64_t kOptimChunk = 4096;
+struct OptimSpan {
+  float* ptr[kOptimStreams];  // sgd: param, grad, momentum_buffer
+  int64_t numel;              // rmsprop: param, grad, square_avg, grad_avg, momentum_buffer
+};
+// first: momentum_buffer = d instead of the momentum update (torch's first step).
+void launch_sgd_step(const OptimSpan* spans, int count, const float* lr, double momentum,
+                     double dampening, bool nesterov, double weight_decay, bool first,
+                     const double* sumsq, double max_norm, double clip_eps, hipStream_t stream);
+void launch_rmsprop_step(const OptimSpan* spans, int count, const float* lr, double alpha,
+                         double eps, double weight_decay, double momentum, bool centered,
+                         const double* sumsq, double max_norm, double clip_eps,
+                         hipStream_t stream);
+
 // Winograd F(2x2,3x3) convolution (3x3, stride 1, pad 1, fp32 NCHW) on f32 MFMA.
 // Transformed weights: U[Rp][Op][16], Rp = wino_pad_reduction(R), Op = wino_pad_output(O).
 // flip = false: w is [O][R][3][3] (forward).  flip = true: w is [R][O][3][3] and the

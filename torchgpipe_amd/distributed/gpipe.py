@@ -122,6 +122,15 @@ class DistributedGPipe:
         (``PipelineStage.clip_grad_norm_``)."""
         return self.stage.clip_grad_norm_(max_norm, norm_type, error_if_nonfinite)
 
+    def optimizer_step(self, optimizer: Optional[torch.optim.Optimizer],
+                       max_grad_norm: Optional[float] = None, norm_type: float = 2.0,
+                       error_if_nonfinite: bool = False) -> Optional[Tensor]:
+        """Clip the whole pipeline's gradient norm and step ``optimizer``; with a bound every
+        rank calls it, one without parameters with ``optimizer=None``
+        (``PipelineStage.optimizer_step``)."""
+        return self.stage.optimizer_step(optimizer, max_grad_norm, norm_type,
+                                         error_if_nonfinite)
+
 
 class DistributedGPipeDataLoader:
     """Stage-aware loader: rank 0 yields ``(data, None)`` and ships the target to the

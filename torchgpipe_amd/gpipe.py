@@ -25,6 +25,7 @@ import torch
 from torch import Tensor, nn
 
 from torchgpipe_amd import microbatch
+from torchgpipe_amd import optim as native_optim
 from torchgpipe_amd.batchnorm import DeferredBatchNorm, set_micro_batches
 from torchgpipe_amd.ops import gradclip
 from torchgpipe_amd.ops.conv import new_step as wino_new_step
@@ -373,6 +374,36 @@ class GPipe(nn.Module):
         """
         return gradclip.clip_grad_norm_(self.parameters(), max_norm, norm_type,
                                         error_if_nonfinite)
+
+    def optimizer_step(self, optimizer: torch.optim.Optimizer,
+                       max_grad_norm: Optional[float] = None, norm_type: float = 2.0,
+                       error_if_nonfinite: bool = False) -> Optional[Tensor]:
+        """Clip the global gradient norm to ``max_grad_norm`` (when set) and step
+        ``optimizer``; returns the norm before clipping (``None`` without a bound).
+
+        With a ``torchgpipe_amd.optim`` optimizer and the Euclidean norm the sum of squares
+        goes to ``optimizer.step(grad_sumsq=..., max_norm=...)``, whose kernel scales each
+        gradient as it loads it: one pass over the gradients less, and **the gradients are
+        left unscaled** (``param.grad`` keeps the unclipped values; the update is bit for
+        bit the clipped one).  Any other optimizer or norm runs :meth:`clip_grad_norm_`
+        followed by ``optimizer.step()``.
+        """
+        if max_grad_norm is None:
+            optimizer.step()
+            return None
+        max_norm, norm_type = float(max_grad_norm), float(norm_type)
+        grads = gradclip.gradients(self.parameters())
+        if norm_type != 2.0 or not grads or not native_optim.is_native(optimizer):
+            norm = self.clip_grad_norm_(max_norm, norm_type, error_if_nonfinite)
+            optimizer.step()
+            return norm
+        with torch.no_grad():
+            total = gradclip.grad_power_sum(grads, norm_type)
+            norm = gradclip.norm_of(total, norm_type)
+            if error_if_nonfinite:
+                gradclip.check_finite(norm, norm_type)
+            optimizer.step(grad_sumsq=total, max_norm=max_norm)  # type: ignore[call-arg]
+            return norm.to(gradclip.result_dtype(grads))
 
     def __getstate__(self) -> Any:
         state = self.__dict__.copy()

@@ -19,7 +19,7 @@ from torch import Tensor
 
 from torchgpipe_amd.ops import _ext
 
-__all__ = ['grad_sumsq', 'scale_grads_', 'grad_power_sum', 'norm_of', 'scale_by_norm_',
+__all__ = ['is_dense', 'grad_sumsq', 'scale_grads_', 'grad_power_sum', 'norm_of', 'scale_by_norm_',
            'gradients', 'result_dtype', 'check_finite', 'clip_grad_norm_', 'grad_norm',
            'clip_info']
 
@@ -31,7 +31,10 @@ def clip_info() -> List[int]:
     return list(_ext.require().grad_clip_info())
 
 
-def _dense(t: Tensor) -> bool:
+def is_dense(t: Tensor) -> bool:
+    """Whether the Python layer hands ``t`` to the multi-tensor kernels as one span of storage:
+    contiguous, channels_last or channels_last_3d.  Narrower than the ops' own check
+    (non-overlapping and dense); other dense permutations take the PyTorch-operation path."""
     if t.is_contiguous():
         return True
     if t.dim() == 4:
@@ -42,7 +45,7 @@ def _dense(t: Tensor) -> bool:
 
 
 def _native(t: Tensor) -> bool:
-    return t.is_cuda and t.dtype in _NATIVE_DTYPES and _dense(t)
+    return t.is_cuda and t.dtype in _NATIVE_DTYPES and is_dense(t)
 
 
 def _split(tensors: Sequence[Tensor]) -> Tuple[List[List[Tensor]], List[Tensor]]:

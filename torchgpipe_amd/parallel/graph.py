@@ -36,8 +36,12 @@ What a replay does not see, and how it is handled:
 * Optimizer hyperparameters are baked into the captured kernels as constants: an LR
   scheduler or a change to ``param_groups`` after the capture would be silently ignored.
   The scalar hyperparameters are snapshotted at capture and every replay checks them;
-  a change raises instead of training with stale values (re-create the StepGraph, or use
-  an optimizer built with ``capturable=True`` and tensor hyperparameters).
+  a change raises instead of training with stale values (re-create the StepGraph).
+  Tensor hyperparameters are read on the device and are not checked: the optimizers of
+  :mod:`torchgpipe_amd.optim` (``SGD``, ``RMSprop``) keep the learning rate in a tensor that
+  ``torch.optim.lr_scheduler`` fills in place, so an LR schedule takes effect between
+  replays; their other hyperparameters are captured constants and still checked.  So is a
+  ``torch.optim`` optimizer built with ``capturable=True`` and a tensor LR.
 
 Shapes first met inside the capture would run the implicit-GEMM kernels' heuristic plans,
 which is why the warm-up steps (which autotune them) come first.
@@ -73,8 +77,10 @@ class StepGraph:
         warmup: eager steps before the capture (allocator pools, autotuned convolution
             plans, optimizer state, lazily initialised libraries).
         max_grad_norm: when set, the global gradient norm is clipped to it between the
-            backward and the optimizer step (``stage.clip_grad_norm_``).  The clip stays on
-            the device, so it is captured and replayed; the bound is a captured constant.
+            backward and the optimizer step (``stage.optimizer_step``: fused into the
+            update of a ``torchgpipe_amd.optim`` optimizer, which leaves ``param.grad``
+            unscaled; ``stage.clip_grad_norm_`` otherwise).  The clip stays on the device,
+            so it is captured and replayed; the bound is a captured constant.
 
     ``step(input, target)`` returns the step's loss tensor, which the next replay
     overwrites.  On a CPU stage every step runs eagerly (there is nothing to capture).
@@ -129,10 +135,10 @@ class StepGraph:
     def _eager(self, input: Tensor, target: Tensor) -> Tensor:
         loss = self.stage.train_step(input, target, self.loss_fn)
         assert loss is not None
-        if self.max_grad_norm is not None:
-            self.stage.clip_grad_norm_(self.max_grad_norm)
         if self.optimizer is not None:
-            self.optimizer.step()
+            self.stage.optimizer_step(self.optimizer, self.max_grad_norm)
+        elif self.max_grad_norm is not None:
+            self.stage.clip_grad_norm_(self.max_grad_norm)
         return loss
 
     def step(self, input: Tensor, target: Tensor) -> Tensor:
@@ -163,8 +169,9 @@ class StepGraph:
         if self._hyperparameters() != self._hyper:
             raise RuntimeError('StepGraph: optimizer hyperparameters changed since the capture '
                                '(the replay would keep the captured values); re-create the '
-                               'StepGraph or use a capturable optimizer with tensor '
-                               'hyperparameters')
+                               'StepGraph, or for a learning-rate schedule use '
+                               'torchgpipe_amd.optim.SGD / RMSprop, whose tensor learning '
+                               'rate is read on the device')
         for param, grad in self._grads:
             if param.grad is not grad:
                 param.grad = grad

@@ -41,6 +41,7 @@ from torch import Tensor, nn
 import torch.distributed as dist
 
 from torchgpipe_amd import microbatch
+from torchgpipe_amd import optim as native_optim
 from torchgpipe_amd.batchnorm import DeferredBatchNorm, set_micro_batches
 from torchgpipe_amd.checkpoint import Checkpointing
 from torchgpipe_amd.gpipe import check_balance, partition_layers, verify_module
@@ -1481,4 +1482,42 @@ class PipelineStage:
             if error_if_nonfinite:
                 gradclip.check_finite(norm, norm_type)
             gradclip.scale_by_norm_(grads, total, max_norm, norm_type)
+            return norm.to(torch.float64 if wide else torch.float32)
+
+    def optimizer_step(self, optimizer: Optional[torch.optim.Optimizer],
+                       max_grad_norm: Optional[float] = None, norm_type: float = 2.0,
+                       error_if_nonfinite: bool = False) -> Optional[Tensor]:
+        """Clip the whole pipeline's gradient norm to ``max_grad_norm`` (when set) and step
+        ``optimizer``; returns the norm before clipping, as :meth:`clip_grad_norm_` does
+        (``None`` without a bound).
+
+        With a bound the call is collective like :meth:`clip_grad_norm_`: every rank makes
+        it, and a rank whose partition has no parameters passes ``optimizer=None``.
+
+        A ``torchgpipe_amd.optim`` optimizer and the Euclidean norm take one pass over the
+        gradients less: the pipeline-wide sum of squares is formed as for
+        :meth:`clip_grad_norm_` (the gloo all-reduce included) and handed to
+        ``optimizer.step(grad_sumsq=..., max_norm=...)``, whose kernel scales each gradient as
+        it loads it.  **The gradients are then left unscaled**: ``param.grad`` holds the
+        unclipped values after the call, while the update is bit for bit the clipped one.
+        Any other optimizer or norm runs :meth:`clip_grad_norm_` followed by
+        ``optimizer.step()``.
+        """
+        if max_grad_norm is None:
+            if optimizer is not None:
+                optimizer.step()
+            return None
+        max_norm, norm_type = float(max_grad_norm), float(norm_type)
+        if optimizer is None or norm_type != 2.0 or not native_optim.is_native(optimizer):
+            norm = self.clip_grad_norm_(max_norm, norm_type, error_if_nonfinite)
+            if optimizer is not None:
+                optimizer.step()
+            return norm
+        with torch.no_grad():
+            grads = gradclip.gradients(self.parameters())
+            total, wide = self._grad_power_sum(grads, norm_type)
+            norm = gradclip.norm_of(total, norm_type)
+            if error_if_nonfinite:
+                gradclip.check_finite(norm, norm_type)
+            optimizer.step(grad_sumsq=total, max_norm=max_norm)  # type: ignore[call-arg]
             return norm.to(torch.float64 if wide else torch.float32)
