@@ -1,20 +1,23 @@
 """Clip-then-step: the native optimizers with the clip fused into the update
 (``grad_sumsq`` + ``torchgpipe_amd.optim`` ``step(grad_sumsq=, max_norm=)``) against
-``ops.gradclip.clip_grad_norm_`` + ``torch.optim`` (foreach; for SGD also ``fused=True``) on
-the parameter lists of U-Net(5,64) and ResNet-101 -- random tensors of the parameters'
-shapes, no training.
+``ops.gradclip.clip_grad_norm_`` + ``torch.optim`` (foreach; for SGD also ``fused=True``, for
+Adam / AdamW ``fused=True, capturable=True``) on the parameter lists of U-Net(5,64) and
+ResNet-101 -- random tensors of the parameters' shapes, no training.
 
-Configurations: SGD with momentum 0.9 and weight decay 1e-4, RMSprop plain, and RMSprop
-centred with momentum 0.9.  The clip is active in every call (``max_norm`` below the norm).
+Configurations: SGD with momentum 0.9 and weight decay 1e-4, RMSprop plain, RMSprop centred
+with momentum 0.9, Adam, and AdamW with amsgrad.  The clip is active in every call
+(``max_norm`` below the norm).
 The implementations alternate window by window in one process; a window is ``--calls``
 back-to-back calls between two device events, and each figure is the median over
 ``--windows`` windows with the min-max spread beside it.  ``gb_s`` is the bytes the native
 path has to move (one read of the gradients for the sum of squares, then one read of the
 gradient and one read and one write of the parameter and of each state tensor) over the time,
 ``share`` that rate over the 6.29 TB/s float4 copy rate of the chip; the other rows use the
-same byte counts so that all can be compared directly.
+same byte counts so that all can be compared directly.  ``native_step_only`` is the update
+kernel alone (``step()`` without a clip), over its own bytes: one read of the gradient, one read
+and one write of the parameter and of each state tensor.
 
-    python benchmarks/optim_bench.py --out profiles/r14/optim/optim.json
+    python benchmarks/optim_bench.py --out profiles/r15/optim/optim.json
 """
 import argparse
 import json
@@ -37,7 +40,12 @@ CONFIGS: Dict[str, Tuple[str, Dict[str, object], int]] = {
     'sgd_momentum_wd': ('sgd', {'momentum': 0.9, 'weight_decay': 1e-4}, 1),
     'rmsprop': ('rmsprop', {}, 1),
     'rmsprop_centered_momentum': ('rmsprop', {'centered': True, 'momentum': 0.9}, 3),
+    'adam': ('adam', {}, 2),
+    'adamw_amsgrad': ('adamw', {'amsgrad': True}, 3),
 }
+NATIVE = {'sgd': optim.SGD, 'rmsprop': optim.RMSprop, 'adam': optim.Adam, 'adamw': optim.AdamW}
+TORCH = {'sgd': torch.optim.SGD, 'rmsprop': torch.optim.RMSprop, 'adam': torch.optim.Adam,
+         'adamw': torch.optim.AdamW}
 
 
 def main() -> None:
@@ -60,6 +68,7 @@ def main() -> None:
         bound = 0.5 * norm
         for config, (kind, kwargs, states) in CONFIGS.items():
             nbytes = 4 * numel * (1 + 1 + 2 * (1 + states))
+            step_bytes = nbytes - 4 * numel
 
             def fresh() -> List[nn.Parameter]:
                 params = [nn.Parameter(torch.randn_like(g)) for g in source]
@@ -73,20 +82,19 @@ def main() -> None:
 
             def add_native() -> None:
                 params = fresh()
-                cls = optim.SGD if kind == 'sgd' else optim.RMSprop
-                opt = cls(params, lr=LR, **kwargs)
+                opt = NATIVE[kind](params, lr=LR, **kwargs)
                 grads = [q.grad for q in params]
 
                 def step() -> None:  # .grad stays unscaled: the bound stays active
                     opt.step(grad_sumsq=gradclip.grad_sumsq(grads), max_norm=bound)
 
                 impls['native_fused_clip'] = step
-                restores['native_fused_clip'] = lambda: None
+                impls['native_step_only'] = opt.step
+                restores['native_fused_clip'] = restores['native_step_only'] = lambda: None
 
             def add_torch(label: str, **extra: object) -> None:
                 params = fresh()
-                cls = torch.optim.SGD if kind == 'sgd' else torch.optim.RMSprop
-                opt = cls(params, lr=LR, **kwargs, **extra)
+                opt = TORCH[kind](params, lr=LR, **kwargs, **extra)
 
                 def step() -> None:
                     # an active bound must stay active over a window: the clip shrinks the
@@ -106,6 +114,8 @@ def main() -> None:
             add_torch('clip_torch_foreach', foreach=True)
             if kind == 'sgd':
                 add_torch('clip_torch_fused', fused=True)
+            elif kind in ('adam', 'adamw'):
+                add_torch('clip_torch_fused_capturable', fused=True, capturable=True)
 
             times: Dict[str, List[float]] = {impl: [] for impl in impls}
             for i in range(a.warmup + a.windows):
@@ -116,12 +126,13 @@ def main() -> None:
                         times[impl].append(ms)
             for impl, ts in times.items():
                 med = statistics.median(ts)
+                moved = step_bytes if impl == 'native_step_only' else nbytes
                 row = {'model': name, 'tensors': len(source), 'elements': numel,
                        'config': config, 'impl': impl, 'ms': round(med, 4),
                        'ms_min': round(min(ts), 4), 'ms_max': round(max(ts), 4),
-                       'window_ms': round(med * a.calls, 2), 'bytes': nbytes,
-                       'gb_s': round(nbytes / med / 1e6, 1),
-                       'share': round(nbytes / (med * 1e-3) / COPY_RATE, 3)}
+                       'window_ms': round(med * a.calls, 2), 'bytes': moved,
+                       'gb_s': round(moved / med / 1e6, 1),
+                       'share': round(moved / (med * 1e-3) / COPY_RATE, 3)}
                 rows.append(row)
                 print(json.dumps(row), flush=True)
             del impls, restores

@@ -371,6 +371,49 @@ void rmsprop_step_(at::TensorList params, at::TensorList grads, at::TensorList s
   if (momentum > 0.0) bump_versions(bufs);
 }
 
+// steps[i]: parameter i's step count, a device fp32 scalar (torch's capturable layout) that the
+// launch advances.  The step of a parameter without elements is left alone.
+void adam_step_(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs,
+                at::TensorList exp_avg_sqs, at::TensorList max_exp_avg_sqs, at::TensorList steps,
+                const at::Tensor& lr, double beta1, double beta2, double eps, double weight_decay,
+                bool decoupled, bool amsgrad, const c10::optional<at::Tensor>& sumsq,
+                double max_norm, double clip_eps) {
+  TORCH_CHECK(amsgrad || max_exp_avg_sqs.empty(),
+              "adam_step_ takes max_exp_avg_sqs only with amsgrad");
+  TORCH_CHECK(steps.size() == params.size(), "adam_step_ takes one step per parameter");
+  std::vector<at::TensorList> lists = {params, grads, exp_avgs, exp_avg_sqs};
+  if (amsgrad) lists.push_back(max_exp_avg_sqs);
+  std::vector<OptimSpan> spans;
+  optim_spans(lists, {0, 1, 2, 3, 4}, "adam_step_", spans);
+  if (params.empty()) return;
+  const auto device = params[0].device();
+  std::vector<float*> step_ptrs;
+  for (size_t i = 0; i < params.size(); ++i) {
+    const at::Tensor& s = steps[i];
+    TORCH_CHECK(s.defined() && s.is_cuda() && s.device() == device &&
+                    s.scalar_type() == at::kFloat && s.numel() == 1,
+                "adam_step_: steps must be float32 scalar tensors on the parameters' device");
+    if (params[i].numel() > 0) step_ptrs.push_back(s.data_ptr<float>());
+  }
+  const float* lr_ptr = optim_lr(lr, device, "adam_step_");
+  const double* sumsq_ptr = optim_sumsq(sumsq, device, "adam_step_");
+  if (spans.empty()) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(device);
+  const int count = static_cast<int>(spans.size());
+  // at::empty: the caching allocator's blocks are safe to take and drop under graph capture
+  auto coef = at::empty({count, kAdamCoefFloats},
+                        at::TensorOptions().dtype(at::kFloat).device(device));
+  launch_adam_step(spans.data(), step_ptrs.data(), count, lr_ptr, beta1, beta2, eps,
+                   weight_decay, decoupled, amsgrad, coef.data_ptr<float>(), sumsq_ptr, max_norm,
+                   clip_eps, at::hip::getCurrentHIPStream(device.index()).stream());
+  check_launched("adam_step_");
+  bump_versions(params);
+  bump_versions(exp_avgs);
+  bump_versions(exp_avg_sqs);
+  if (amsgrad) bump_versions(max_exp_avg_sqs);
+  bump_versions(steps);
+}
+
 // (chunk elements, tensors per launch, threads per block)
 std::vector<int64_t> optim_info() {
   return {kOptimChunk, kOptimTensors, kOptimThreads};
@@ -737,6 +780,11 @@ TORCH_LIBRARY(tgpipe, m) {
         "Tensor(c!)[] grad_avgs, Tensor(d!)[] bufs, Tensor lr, float alpha, float eps, "
         "float weight_decay, float momentum, bool centered, Tensor? sumsq, float max_norm, "
         "float clip_eps) -> ()");
+  // steps: per parameter a device fp32 scalar, advanced by the launch; decoupled: AdamW
+  m.def("adam_step_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, "
+        "Tensor(c!)[] exp_avg_sqs, Tensor(d!)[] max_exp_avg_sqs, Tensor(e!)[] steps, Tensor lr, "
+        "float beta1, float beta2, float eps, float weight_decay, bool decoupled, "
+        "bool amsgrad, Tensor? sumsq, float max_norm, float clip_eps) -> ()");
   // [chunk elements, tensors per launch, threads per block]
   m.def("optim_info() -> int[]", &tgpipe::optim_info);
   m.def("wino_weight(Tensor w, bool flip, Tensor? out=None) -> Tensor");
@@ -774,6 +822,7 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("grad_scale_", &tgpipe::grad_scale_);
   m.impl("sgd_step_", &tgpipe::sgd_step_);
   m.impl("rmsprop_step_", &tgpipe::rmsprop_step_);
+  m.impl("adam_step_", &tgpipe::adam_step_);
   m.impl("wino_weight", &tgpipe::wino_weight);
   m.impl("wino_conv", &tgpipe::wino_conv);
   m.impl("wino_wgrad", &tgpipe::wino_wgrad);

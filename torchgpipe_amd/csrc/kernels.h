@@ -109,7 +109,7 @@ constexpr int64_t kOptimChunk = 4096;
 struct OptimSpan {
   float* ptr[kOptimStreams];  // sgd: param, grad, momentum_buffer
   int64_t numel;              // rmsprop: param, grad, square_avg, grad_avg, momentum_buffer
-};
+};                            // adam: param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq
 // first: momentum_buffer = d instead of the momentum update (torch's first step).
 void launch_sgd_step(const OptimSpan* spans, int count, const float* lr, double momentum,
                      double dampening, bool nesterov, double weight_decay, bool first,
@@ -118,6 +118,14 @@ void launch_rmsprop_step(const OptimSpan* spans, int count, const float* lr, dou
                          double eps, double weight_decay, double momentum, bool centered,
                          const double* sumsq, double max_norm, double clip_eps,
                          hipStream_t stream);
+// Adam / AdamW (decoupled).  steps[i]: tensor i's step count, a device fp32 scalar that the
+// launch advances by one before the update reads it, so every tensor gets the bias correction
+// of its own count.  `coef`: a device workspace of kAdamCoefFloats floats per tensor.
+constexpr int kAdamCoefFloats = 4;
+void launch_adam_step(const OptimSpan* spans, float* const* steps, int count, const float* lr,
+                      double beta1, double beta2, double eps, double weight_decay,
+                      bool decoupled, bool amsgrad, float* coef, const double* sumsq,
+                      double max_norm, double clip_eps, hipStream_t stream);
 
 // Winograd F(2x2,3x3) convolution (3x3, stride 1, pad 1, fp32 NCHW) on f32 MFMA.
 // Transformed weights: U[Rp][Op][16], Rp = wino_pad_reduction(R), Op = wino_pad_output(O).

@@ -6,6 +6,11 @@
 //                  centred: ga = lerp(ga, d, 1 - alpha), avg = sqrt(sq - ga * ga) + eps,
 //                  otherwise avg = sqrt(sq) + eps;
 //                  buf = mu * buf + d / avg, p -= lr * buf            (no momentum: p -= lr * d / avg)
+//   adam_step:     coupled decay: d = g + wd * p;  decoupled (AdamW): d = g, p *= 1 - lr * wd;
+//                  m = lerp(m, d, 1 - beta1);  v = beta2 * v + (1 - beta2) * d * d;
+//                  amsgrad: vmax = maximum(vmax, v) (NaN from either side) and v' = vmax,
+//                  otherwise v' = v;  with t the tensor's own step count, advanced first,
+//                  p -= lr / (1 - beta1^t) * m / (sqrt(v') / sqrt(1 - beta2^t) + eps)
 //
 // in the order of torch/optim's single-tensor loops.  One pass: `grad` is read once, `param`
 // and every state tensor are read once and written once.
@@ -33,8 +38,22 @@
 // scratch: 6 / 4 / 4 / 4 / 4 / 3 waves per SIMD, i.e. at least three 256-lane blocks per CU,
 // each with 32 - 80 KiB of loads in flight -- several times the 32 KiB per CU that streaming
 // takes, with blocks left over to hide the stores.
+//
+// Adam keeps its step counts on the device, one fp32 scalar per tensor (the layout of
+// torch.optim.Adam(capturable=True)), so a captured step advances them.  Ahead of each launch
+// of adam_step_kernel, adam_advance_kernel runs one lane per tensor of the table: it adds one
+// to the tensor's count, forms lr / (1 - beta1^t), sqrt(1 - beta2^t) and 1 - lr * wd in fp64
+// -- what torch's host code computes as Python floats -- and rounds each once into the
+// tensor's row of a workspace (AdamCoef).  A block of the main kernel reads the row of the
+// tensor chunk_of found: no block runs pow, none races with the increment, and tensors whose
+// counts differ (a parameter that had no gradient in some step lags) share a launch.  The
+// update kernels compile to 128 VGPRs (four streams) and 136 (amsgrad, five), without scratch:
+// 4 / 3 waves per SIMD, as the RMSprop kernels of as many streams; adam_advance_kernel to 44
+// VGPRs without scratch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
 
 #include "kernels.h"
 
@@ -54,6 +73,14 @@ struct OptimTable {
   int32_t count;
 };
 
+// What adam_advance_kernel leaves for the blocks of one tensor, each rounded from fp64 once.
+struct AdamCoef {
+  float step_size;  // lr / (1 - beta1^t)
+  float bc2_sqrt;   // sqrt(1 - beta2^t)
+  float decay;      // 1 - lr * weight_decay (decoupled)
+  float unused;
+};
+
 // What every block reads besides the table.
 struct StepArgs {
   const float* lr;
@@ -65,9 +92,15 @@ struct StepArgs {
   float weight_decay;
   float alpha;       // RMSprop
   float alpha_rest;  // RMSprop: 1 - alpha
-  float eps;         // RMSprop
+  float eps;         // RMSprop, Adam
   int nesterov;
   int first;
+  // Adam
+  const AdamCoef* coef;  // one row per tensor of the table
+  float beta1_rest;      // 1 - beta1
+  float beta2;
+  float beta2_rest;      // 1 - beta2
+  int decoupled;         // AdamW's decay, and weight_decay != 0
 };
 static_assert(sizeof(OptimTable) + sizeof(StepArgs) <= 3200,
               "table + arguments + implicit arguments < 4 KB");
@@ -76,6 +109,7 @@ static_assert(sizeof(OptimTable) + sizeof(StepArgs) <= 3200,
 template <int NS>
 struct Chunk {
   float* base[NS];
+  int tensor;  // its position in the table
   int valid;
   bool vector;  // a full chunk, every base 16-byte aligned
 };
@@ -90,6 +124,7 @@ __device__ __forceinline__ Chunk<NS> chunk_of(const OptimTable& table, const int
     if (table.first[mid] <= b) lo = mid; else hi = mid;
   }
   Chunk<NS> c;
+  c.tensor = lo;
   const int64_t offset = static_cast<int64_t>(b - table.first[lo]) * kChunk;
   uintptr_t bits = 0;
 #pragma unroll
@@ -234,14 +269,40 @@ __device__ __forceinline__ void rmsprop_elem(float& p, float g, float* state, co
   }
 }
 
-// Applies `elem(p, g, state[], ...)` to every element of the block's chunk.  NS streams:
-// 0 param, 1 grad, 2.. state.
+// torch.maximum: a NaN on either side is the result (fmaxf would return the other operand).
+__device__ __forceinline__ float maximum_like_torch(float a, float b) {
+  return (a > b || a != a) ? a : b;
+}
+
+template <bool AMSGRAD>
+__device__ __forceinline__ void adam_elem(float& p, float g, float* state, const Clip& clip,
+                                          const AdamCoef& k, const StepArgs& a) {
+  // state: [0] exp_avg, [1] exp_avg_sq, [2] max_exp_avg_sq (amsgrad)
+  float d;
+  if (a.decoupled) {
+    p = p * k.decay;  // p.mul_(1 - lr * wd)
+    d = clip.active ? __fmul_rn(g, clip.f) : g;
+  } else {
+    d = decayed(g, p, clip, a.weight_decay);
+  }
+  const float m = lerp_like_torch(state[0], d, a.beta1_rest);  // m.lerp_(d, 1 - beta1)
+  state[0] = m;
+  // v.mul_(beta2).addcmul_(d, d, value=1 - beta2)
+  float v = fmaf(a.beta2_rest * d, d, a.beta2 * state[1]);
+  state[1] = v;
+  if (AMSGRAD) {
+    v = maximum_like_torch(state[2], v);
+    state[2] = v;
+  }
+  const float denom = sqrtf(v) / k.bc2_sqrt + a.eps;  // (v.sqrt() / bc2_sqrt).add_(eps)
+  p = p + (-k.step_size * m) / denom;                  // p.addcdiv_(m, denom, value=-step_size)
+}
+
+// Applies `elem(p, g, state[], ...)` to every element of chunk `c`.  NS streams: 0 param,
+// 1 grad, 2.. state.
 template <int NS, typename F>
-__device__ __forceinline__ void step_chunk(const OptimTable& table, const StepArgs& a,
-                                           const int (&rows)[NS], F elem) {
-  const Clip clip = clip_of(a);
-  const float lr = a.lr[0];
-  const Chunk<NS> c = chunk_of<NS>(table, rows);
+__device__ __forceinline__ void apply_chunk(const Chunk<NS>& c, const Clip& clip, float lr,
+                                            const StepArgs& a, F elem) {
   float4 raw[NS][kLoads];
   load_chunk<NS>(c, raw);
 #pragma unroll
@@ -264,6 +325,16 @@ __device__ __forceinline__ void step_chunk(const OptimTable& table, const StepAr
     for (int s = 0; s < NS; ++s) raw[s][i] = make_float4(v[s][0], v[s][1], v[s][2], v[s][3]);
   }
   store_chunk<NS>(c, raw);
+}
+
+// apply_chunk on the block's own chunk.
+template <int NS, typename F>
+__device__ __forceinline__ void step_chunk(const OptimTable& table, const StepArgs& a,
+                                           const int (&rows)[NS], F elem) {
+  const Clip clip = clip_of(a);
+  const float lr = a.lr[0];
+  const Chunk<NS> c = chunk_of<NS>(table, rows);
+  apply_chunk<NS>(c, clip, lr, a, elem);
 }
 
 template <bool MOMENTUM>
@@ -292,6 +363,57 @@ __global__ __launch_bounds__(kThreads) void rmsprop_step_kernel(OptimTable table
                     const StepArgs& args) {
                    rmsprop_elem<CENTERED, MOMENTUM>(p, g, state, clip, lr, args);
                  });
+}
+
+// The step counts of one table's tensors, and what adam_advance_kernel needs besides.
+struct AdamSteps {
+  float* step[kOptimTensors];
+  int32_t count;
+};
+struct AdvanceArgs {
+  const float* lr;
+  AdamCoef* coef;
+  double beta1;
+  double beta2;
+  double weight_decay;  // 0 unless decoupled
+};
+
+// The Adam kernels are built without the packed fp32 instructions (v_pk_*_f32).
+#define NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+
+// One lane per tensor: count += 1, then the tensor's coefficients in fp64, rounded once.
+NO_PACKED_F32 __global__ __launch_bounds__(kOptimTensors) void adam_advance_kernel(AdamSteps steps,
+                                                                     AdvanceArgs a) {
+  const int t = static_cast<int>(threadIdx.x);
+  if (t >= steps.count) return;
+  const float count = steps.step[t][0] + 1.0f;
+  steps.step[t][0] = count;
+  const double step = static_cast<double>(count);
+  const double lr = static_cast<double>(a.lr[0]);
+  AdamCoef k;
+  k.step_size = static_cast<float>(lr / (1.0 - pow(a.beta1, step)));
+  k.bc2_sqrt = static_cast<float>(sqrt(1.0 - pow(a.beta2, step)));
+  k.decay = static_cast<float>(1.0 - lr * a.weight_decay);
+  k.unused = 0.0f;
+  a.coef[t] = k;
+}
+
+// Table rows: 0 param, 1 grad, 2 exp_avg, 3 exp_avg_sq, 4 max_exp_avg_sq.
+template <bool AMSGRAD>
+NO_PACKED_F32 __global__ __launch_bounds__(kThreads) void adam_step_kernel(OptimTable table,
+                                                                           StepArgs a) {
+  constexpr int NS = AMSGRAD ? 5 : 4;
+  int rows[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) rows[s] = s;
+  const Clip clip = clip_of(a);
+  const Chunk<NS> c = chunk_of<NS>(table, rows);
+  const AdamCoef k = a.coef[c.tensor];  // uniform over the block; the rate is folded in
+  apply_chunk<NS>(c, clip, 0.0f, a,
+                  [k](float& p, float g, float* state, const Clip& clip, float,
+                      const StepArgs& args) {
+                    adam_elem<AMSGRAD>(p, g, state, clip, k, args);
+                  });
 }
 
 // Calls launch(table, blocks) for each table's worth of `spans`.
@@ -368,6 +490,46 @@ void launch_rmsprop_step(const OptimSpan* spans, int count, const float* lr, dou
       hipLaunchKernelGGL((rmsprop_step_kernel<false, true>), g, b, 0, stream, table, a);
     } else {
       hipLaunchKernelGGL((rmsprop_step_kernel<false, false>), g, b, 0, stream, table, a);
+    }
+  });
+}
+
+void launch_adam_step(const OptimSpan* spans, float* const* steps, int count, const float* lr,
+                      double beta1, double beta2, double eps, double weight_decay,
+                      bool decoupled, bool amsgrad, float* coef, const double* sumsq,
+                      double max_norm, double clip_eps, hipStream_t stream) {
+  static_assert(sizeof(AdamCoef) == kAdamCoefFloats * sizeof(float), "workspace row");
+  StepArgs a = common_args(lr, sumsq, max_norm, clip_eps, 0.0, weight_decay);
+  a.beta1_rest = static_cast<float>(1.0 - beta1);
+  a.beta2 = static_cast<float>(beta2);
+  a.beta2_rest = static_cast<float>(1.0 - beta2);
+  a.eps = static_cast<float>(eps);
+  a.decoupled = decoupled && weight_decay != 0.0 ? 1 : 0;
+  AdvanceArgs adv{lr, nullptr, beta1, beta2, decoupled ? weight_decay : 0.0};
+  // for_each_table skips what has no elements: it must see the tensors that the steps and the
+  // workspace rows are counted by
+  std::vector<OptimSpan> live;
+  std::vector<float*> live_steps;
+  for (int i = 0; i < count; ++i) {
+    if (spans[i].numel <= 0) continue;
+    live.push_back(spans[i]);
+    live_steps.push_back(steps[i]);
+  }
+  int done = 0;  // tensors in earlier tables
+  for_each_table(live.data(), static_cast<int>(live.size()),
+                 [&](const OptimTable& table, unsigned grid) {
+    AdamSteps st{};
+    st.count = table.count;
+    for (int t = 0; t < table.count; ++t) st.step[t] = live_steps[done + t];
+    adv.coef = reinterpret_cast<AdamCoef*>(coef) + done;
+    a.coef = adv.coef;
+    done += table.count;
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(kOptimTensors), 0, stream, st, adv);
+    const dim3 g(grid), b(kThreads);
+    if (amsgrad) {
+      hipLaunchKernelGGL(adam_step_kernel<true>, g, b, 0, stream, table, a);
+    } else {
+      hipLaunchKernelGGL(adam_step_kernel<false>, g, b, 0, stream, table, a);
     }
   });
 }

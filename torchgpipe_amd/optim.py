@@ -1,9 +1,11 @@
-"""Optimizers whose step is one native pass (``csrc/optim.hip``): :class:`SGD`, :class:`RMSprop`.
+"""Optimizers whose step is one native pass (``csrc/optim.hip``): :class:`SGD`,
+:class:`RMSprop`, :class:`Adam`, :class:`AdamW`.
 
-Both subclass their ``torch.optim`` namesakes -- ``param_groups``, ``state_dict`` /
+All subclass their ``torch.optim`` namesakes -- ``param_groups``, ``state_dict`` /
 ``load_state_dict``, ``isinstance`` and the state keys (``momentum_buffer``; ``square_avg``,
-``grad_avg``, ``momentum_buffer``, ``step``) are torch's, and a state dict moves between the
-two classes in both directions -- and differ in three ways:
+``grad_avg``, ``momentum_buffer``, ``step``; ``exp_avg``, ``exp_avg_sq``, ``max_exp_avg_sq``,
+``step``) are torch's, and a state dict moves between the two classes in both directions --
+and differ in three ways:
 
 * **The learning rate is a tensor.**  ``group['lr']`` is a 0-dim fp32 tensor on the device of
   the group's first parameter, and the kernels read it there.  ``torch.optim.lr_scheduler``
@@ -26,9 +28,13 @@ single-tensor loops (the ``_ext`` convention: the CPU path is the oracle of the 
 on fp32 CPU tensors it is bitwise ``torch.optim``'s ``foreach=False``).  A GPU parameter the
 kernels take raises when the extension is not built, like every native op.
 
-``maximize``, ``differentiable``, ``capturable`` and ``fused`` are refused.  RMSprop's
-``step`` counter (which its update never reads) is advanced on the host when ``step()`` runs
-in Python: replays of a captured graph do not advance it.
+``maximize``, ``differentiable``, ``capturable``, ``fused`` and tensor ``betas`` are refused.
+RMSprop's ``step`` counter (which its update never reads) is advanced on the host when
+``step()`` runs in Python: replays of a captured graph do not advance it.  Adam's and AdamW's
+bias corrections do read the count, so for a GPU parameter ``step`` is a 0-dim fp32 tensor on
+the parameter's device (the layout of ``torch.optim.Adam(capturable=True)``): the kernel
+launch advances it and forms each tensor's corrections from it on the device, in fp64, and a
+captured step therefore counts its replays.
 """
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple, Union
 
@@ -38,7 +44,7 @@ from torch import Tensor
 from torchgpipe_amd.ops import _ext
 from torchgpipe_amd.ops.gradclip import is_dense
 
-__all__ = ['SGD', 'RMSprop', 'is_native', 'optim_info']
+__all__ = ['SGD', 'RMSprop', 'Adam', 'AdamW', 'is_native', 'optim_info']
 
 Params = Union[Iterable[Tensor], Iterable[Dict[str, Any]]]
 
@@ -313,3 +319,136 @@ class RMSprop(_Native, torch.optim.RMSprop):
             _ext.require(native[0][0]).rmsprop_step_(
                 native[0], native[1], native[2], native[3], native[4], lr, alpha, eps, wd,
                 momentum, centered, clip.on(lr.device), clip.max_norm, clip.eps)
+
+
+class _AdamBase(_Native):
+    """The step of :class:`Adam` and :class:`AdamW` (``group['decoupled_weight_decay']``)."""
+
+    @staticmethod
+    def _refuse_adam(betas: Tuple[Any, Any], **flags: Any) -> None:
+        _Native._refuse(flags)
+        if isinstance(betas[0], Tensor) or isinstance(betas[1], Tensor):
+            raise ValueError('torchgpipe_amd.optim does not support tensor betas '
+                             '(use the torch.optim class)')
+
+    @staticmethod
+    def _device_step(p: Tensor, state: Dict[str, Any]) -> None:
+        """A GPU parameter's ``step`` as an fp32 scalar on the parameter's device."""
+        step = state.get('step')
+        if p.is_cuda and step is not None and not (
+                isinstance(step, Tensor) and step.device == p.device
+                and step.dtype == torch.float32 and step.dim() == 0):
+            state['step'] = torch.as_tensor(step, dtype=torch.float32).reshape(()).to(p.device)
+
+    def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
+        """As :meth:`_Native.load_state_dict`; a state dict of ``torch.optim.Adam`` / ``AdamW``
+        loads whatever its ``capturable`` (the steps move to their parameters' devices)."""
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            group['capturable'] = False
+            group['foreach'] = False
+            for p in group['params']:
+                if p in self.state:
+                    self._device_step(p, self.state[p])
+
+    def _state_of(self, p: Tensor, amsgrad: bool) -> Dict[str, Any]:
+        state = self.state[p]
+        if len(state) == 0:  # torch's Adam._init_group, the step as with capturable=True
+            state['step'] = (torch.zeros((), dtype=torch.float32, device=p.device) if p.is_cuda
+                             else torch.zeros((), dtype=torch.get_default_dtype()))
+            state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if amsgrad:
+                state['max_exp_avg_sq'] = torch.zeros_like(
+                    p, memory_format=torch.preserve_format)
+        else:
+            self._device_step(p, state)
+        return state
+
+    def _step_device(self, group: Dict[str, Any], params: List[Tensor], lr: Tensor,
+                     clip: _Clip) -> None:
+        beta1, beta2 = (float(b) for b in group['betas'])
+        eps, wd = float(group['eps']), float(group['weight_decay'])
+        amsgrad, decoupled = bool(group['amsgrad']), bool(group['decoupled_weight_decay'])
+        native: List[List[Tensor]] = [[], [], [], [], [], []]
+        for p in params:
+            g = p.grad
+            state = self._state_of(p, amsgrad)
+            m, v, step = state['exp_avg'], state['exp_avg_sq'], state['step']
+            vmax = state['max_exp_avg_sq'] if amsgrad else None
+            tensors = [t for t in (p, g, m, v, vmax) if t is not None]
+            if _kernel_takes(p, tensors[1:]):
+                for lst, t in zip(native, (p, g, m, v, vmax, step)):
+                    if t is not None:
+                        lst.append(t)
+                continue
+            # torch's _single_tensor_adam: on the CPU its non-capturable branch with host
+            # floats; on a GPU the coefficients stay on the device (no host read), formed in
+            # fp64 and rounded once as adam_advance_kernel forms them
+            step += 1
+            d = clip.apply(g)
+            host = not p.is_cuda
+            rate: Any = float(lr) if host else lr.double()
+            if wd != 0:
+                if decoupled:
+                    p.mul_(1 - rate * wd if host else (1 - rate * wd).to(p.dtype))
+                else:
+                    d = d.add(p, alpha=wd)
+            m.lerp_(d, 1 - beta1)
+            v.mul_(beta2).addcmul_(d, d, value=1 - beta2)
+            count: Any = float(step) if host else step.double()
+            step_size = rate / (1 - beta1 ** count)
+            bc2_sqrt = (1 - beta2 ** count) ** 0.5
+            if vmax is not None:
+                torch.maximum(vmax, v, out=vmax)
+                v = vmax
+            if host:
+                denom = (v.sqrt() / bc2_sqrt).add_(eps)
+                p.addcdiv_(m, denom, value=-step_size)
+            else:
+                denom = (v.sqrt() / bc2_sqrt.to(p.dtype)).add_(eps)
+                p.addcdiv_(m * (-step_size).to(p.dtype), denom)
+        if native[0]:
+            _ext.require(native[0][0]).adam_step_(
+                native[0], native[1], native[2], native[3], native[4], native[5], lr, beta1,
+                beta2, eps, wd, decoupled, amsgrad, clip.on(lr.device), clip.max_norm, clip.eps)
+
+
+class Adam(_AdamBase, torch.optim.Adam):
+    """``torch.optim.Adam`` on the native one-pass kernel, with a device-resident LR and
+    device-resident step counts.
+
+    Arguments as ``torch.optim.Adam`` (``foreach`` is accepted and ignored).  See the module
+    docstring for ``step(grad_sumsq=, max_norm=)``, the ``step`` state entry and what falls
+    back to PyTorch operations.
+    """
+
+    def __init__(self, params: Params, lr: Union[float, Tensor] = 1e-3,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0, amsgrad: bool = False, *,
+                 foreach: Optional[bool] = None, maximize: bool = False,
+                 capturable: bool = False, differentiable: bool = False,
+                 fused: Optional[bool] = None, decoupled_weight_decay: bool = False) -> None:
+        self._refuse_adam(betas, maximize=maximize, differentiable=differentiable,
+                          capturable=capturable, fused=fused)
+        torch.optim.Adam.__init__(self, params, lr=float(lr), betas=betas, eps=eps,
+                                  weight_decay=weight_decay, amsgrad=amsgrad, foreach=False,
+                                  decoupled_weight_decay=decoupled_weight_decay)
+        self._tensor_lrs()
+
+
+class AdamW(_AdamBase, torch.optim.AdamW):
+    """``torch.optim.AdamW`` (decoupled weight decay) on the native one-pass kernel; see
+    :class:`Adam`."""
+
+    def __init__(self, params: Params, lr: Union[float, Tensor] = 1e-3,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, amsgrad: bool = False, *,
+                 maximize: bool = False, foreach: Optional[bool] = None,
+                 capturable: bool = False, differentiable: bool = False,
+                 fused: Optional[bool] = None) -> None:
+        self._refuse_adam(betas, maximize=maximize, differentiable=differentiable,
+                          capturable=capturable, fused=fused)
+        torch.optim.AdamW.__init__(self, params, lr=float(lr), betas=betas, eps=eps,
+                                   weight_decay=weight_decay, amsgrad=amsgrad, foreach=False)
+        self._tensor_lrs()

@@ -38,10 +38,12 @@ What a replay does not see, and how it is handled:
   The scalar hyperparameters are snapshotted at capture and every replay checks them;
   a change raises instead of training with stale values (re-create the StepGraph).
   Tensor hyperparameters are read on the device and are not checked: the optimizers of
-  :mod:`torchgpipe_amd.optim` (``SGD``, ``RMSprop``) keep the learning rate in a tensor that
-  ``torch.optim.lr_scheduler`` fills in place, so an LR schedule takes effect between
-  replays; their other hyperparameters are captured constants and still checked.  So is a
-  ``torch.optim`` optimizer built with ``capturable=True`` and a tensor LR.
+  :mod:`torchgpipe_amd.optim` (``SGD``, ``RMSprop``, ``Adam``, ``AdamW``) keep the learning
+  rate in a tensor that ``torch.optim.lr_scheduler`` fills in place, so an LR schedule takes
+  effect between replays; their other hyperparameters are captured constants and still
+  checked.  So is a ``torch.optim`` optimizer built with ``capturable=True`` and a tensor LR.
+  ``Adam`` / ``AdamW`` also keep each parameter's step count in a device tensor that the
+  captured update advances, so the bias corrections follow the replays.
 
 Shapes first met inside the capture would run the implicit-GEMM kernels' heuristic plans,
 which is why the warm-up steps (which autotune them) come first.
@@ -170,8 +172,8 @@ class StepGraph:
             raise RuntimeError('StepGraph: optimizer hyperparameters changed since the capture '
                                '(the replay would keep the captured values); re-create the '
                                'StepGraph, or for a learning-rate schedule use '
-                               'torchgpipe_amd.optim.SGD / RMSprop, whose tensor learning '
-                               'rate is read on the device')
+                               'torchgpipe_amd.optim.SGD / RMSprop / Adam / AdamW, whose '
+                               'tensor learning rate is read on the device')
         for param, grad in self._grads:
             if param.grad is not grad:
                 param.grad = grad
