@@ -28,7 +28,10 @@ ROCM = os.environ.get('ROCM_PATH', '/opt/rocm')
 
 KERNEL_SOURCES = ['kernels.hip', 'winograd.hip', 'winograd_f4.hip', 'conv_gemm.hip',
                   'batchnorm.hip', 'pool.hip', 'unet_ops.hip', 'gradclip.hip', 'wire.hip',
-                  'optim.hip']
+                  'optim.hip', 'linear.hip']
+# extra hipcc flags per kernel source.  linear.hip: no packed-f32 VALU forms (v_pk_*_f32) for
+# its float4 epilogue adds -- plain f32 adds, rounded as the scalar path rounds them
+KERNEL_FLAGS = {'linear.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 HOST_SOURCES = ['bindings.cpp', 'convbn.cpp']
 HEADERS = ['kernels.h', 'philox.h', 'bf16_round.h']
 HOST_HEADERS = ['aten_checks.h']  # ATen-side helpers: the host sources only
@@ -88,7 +91,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(BUILD, src + '.o')
         if force or _stale(obj, [path] + headers):
             _run([hipcc(), f'--offload-arch={ARCH}', *common, '-munsafe-fp-atomics',
-                  '-c', path, '-o', obj], verbose)
+                  *KERNEL_FLAGS.get(src, []), '-c', path, '-o', obj], verbose)
             relink = True
         objects.append(obj)
 

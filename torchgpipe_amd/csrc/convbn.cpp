@@ -1861,6 +1861,97 @@ at::Tensor maxpool2x2_backward(const at::Tensor& x_in, const at::Tensor& dy_in) 
   return dx;
 }
 
+// ---- nn.Linear on the split-bf16 GEMM (linear.hip) ------------------------------------------
+// x [..., I], w [O][I], y [..., O]; the leading dimensions are flattened into R rows.
+
+int linear_rows(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.dim() >= 1 && t.numel() > 0, name, " must have at least one dimension and one "
+              "element");
+  return static_cast<int>(t.numel() / t.size(-1));
+}
+
+void linear_gemm(int pass, const at::Tensor& a, const at::Tensor& b, const float* bias,
+                 at::Tensor& out, int M, int N, int K, bool accumulate) {
+  const LinearPlan plan = linear_plan(M, N, K);
+  const int64_t ws_size = linear_workspace(M, N, plan);
+  at::Tensor ws;  // from the caching allocator, on the current stream
+  if (ws_size > 0) ws = at::empty({ws_size}, out.options());
+  launch_linear_gemm(pass, a.data_ptr<float>(), b.data_ptr<float>(), bias,
+                     out.data_ptr<float>(), M, N, K, plan, accumulate,
+                     ws_size > 0 ? ws.data_ptr<float>() : nullptr, cur_stream(out));
+}
+
+std::vector<int64_t> with_last(const at::Tensor& t, int64_t last) {
+  std::vector<int64_t> shape(t.sizes().begin(), t.sizes().end());
+  shape.back() = last;
+  return shape;
+}
+
+at::Tensor linear_forward(const at::Tensor& x, const at::Tensor& w,
+                          const c10::optional<at::Tensor>& b) {
+  check_f32(x, "x", x);
+  check_f32(w, "weight", x);
+  TORCH_CHECK(w.dim() == 2 && x.dim() >= 1 && x.size(-1) == w.size(1),
+              "linear_forward: x [..., I] and weight [O][I] do not match");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const int R = linear_rows(x, "x"), I = static_cast<int>(w.size(1)),
+            O = static_cast<int>(w.size(0));
+  const float* bias = opt_ptr(b, "bias", x, O);
+  auto y = at::empty(with_last(x, O), x.options());
+  check_f32(y, "y", x);
+  linear_gemm(0, x, w, bias, y, R, O, I, false);
+  return y;
+}
+
+at::Tensor linear_backward_data(const at::Tensor& dy, const at::Tensor& w) {
+  check_f32(dy, "dy", dy);
+  check_f32(w, "weight", dy);
+  TORCH_CHECK(w.dim() == 2 && dy.dim() >= 1 && dy.size(-1) == w.size(0),
+              "linear_backward_data: dy [..., O] and weight [O][I] do not match");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  const int R = linear_rows(dy, "dy"), I = static_cast<int>(w.size(1)),
+            O = static_cast<int>(w.size(0));
+  auto dx = at::empty(with_last(dy, I), dy.options());
+  check_f32(dx, "dx", dy);
+  linear_gemm(1, dy, w, nullptr, dx, R, I, O, false);
+  return dx;
+}
+
+// dw [O][I] = dy^T x: a fresh tensor, or `into` -- stored, or with `accumulate` added to
+// (the beta = 1 of an addmm_ into .grad).
+at::Tensor linear_backward_weight(const at::Tensor& dy, const at::Tensor& x,
+                                  const c10::optional<at::Tensor>& into, bool accumulate) {
+  check_f32(dy, "dy", dy);
+  check_f32(x, "x", dy);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  const int R = linear_rows(dy, "dy"), O = static_cast<int>(dy.size(-1)),
+            I = static_cast<int>(x.size(-1));
+  TORCH_CHECK(linear_rows(x, "x") == R, "linear_backward_weight: dy and x differ in rows");
+  const bool given = into.has_value() && into->defined();
+  TORCH_CHECK(given || !accumulate, "linear_backward_weight: accumulate needs `into`");
+  at::Tensor dw = given ? *into : at::empty({O, I}, dy.options());
+  check_f32(dw, "into", dy);
+  TORCH_CHECK(dw.dim() == 2 && dw.size(0) == O && dw.size(1) == I,
+              "linear_backward_weight: `into` must be [O][I]");
+  linear_gemm(2, dy, x, nullptr, dw, O, I, R, accumulate);
+  return dw;
+}
+
+at::Tensor linear_bias_grad(const at::Tensor& dy, const c10::optional<at::Tensor>& into,
+                            bool accumulate) {
+  check_f32(dy, "dy", dy);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  const int R = linear_rows(dy, "dy"), O = static_cast<int>(dy.size(-1));
+  const bool given = into.has_value() && into->defined();
+  TORCH_CHECK(given || !accumulate, "linear_bias_grad: accumulate needs `into`");
+  at::Tensor db = given ? *into : at::empty({O}, dy.options());
+  check_f32(db, "into", dy);
+  TORCH_CHECK(db.numel() == O, "linear_bias_grad: `into` must have O elements");
+  launch_linear_bias_grad(dy.data_ptr<float>(), db.data_ptr<float>(), R, O, accumulate,
+                          cur_stream(dy));
+  return db;
+}
+
 }  // namespace
 }  // namespace tgpipe
 
@@ -1925,6 +2016,14 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
         "Tensor? weight_t=None) -> Tensor");
   m.def("conv_gemm_backward_weight(Tensor dz, Tensor x, Tensor weight, int[] geo, bool relu, "
         "Tensor? accum=None, Tensor? slab=None, bool slab_first=False) -> Tensor");
+  m.def("linear_forward(Tensor x, Tensor weight, Tensor? bias=None) -> Tensor");
+  m.def("linear_backward_data(Tensor dy, Tensor weight) -> Tensor");
+  m.def("linear_backward_weight(Tensor dy, Tensor x, Tensor? into=None, "
+        "bool accumulate=False) -> Tensor");
+  m.def("linear_bias_grad(Tensor dy, Tensor? into=None, bool accumulate=False) -> Tensor");
+  m.def("linear_force_plan(int tile, int splits) -> ()", [](int64_t tile, int64_t splits) {
+    tgpipe::linear_force_plan(static_cast<int>(tile), static_cast<int>(splits));
+  });
 }
 
 TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
@@ -1940,6 +2039,10 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("conv_gemm_sweep", &tgpipe::conv_gemm_sweep);
   m.impl("conv_gemm_backward_data", &tgpipe::conv_gemm_backward_data);
   m.impl("conv_gemm_backward_weight", &tgpipe::conv_gemm_backward_weight);
+  m.impl("linear_forward", &tgpipe::linear_forward);
+  m.impl("linear_backward_data", &tgpipe::linear_backward_data);
+  m.impl("linear_backward_weight", &tgpipe::linear_backward_weight);
+  m.impl("linear_bias_grad", &tgpipe::linear_bias_grad);
   m.impl("bn_train_forward", &tgpipe::bn_train_forward);
   m.impl("bn_train_backward", &tgpipe::bn_train_backward);
   m.impl("dbn_commit64", &tgpipe::dbn_commit64);

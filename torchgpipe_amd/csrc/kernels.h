@@ -376,6 +376,29 @@ struct SlabFlushEntry {
 // grad (+)= sum_s slab[s] for every entry (ceil(count / kSlabFlushMax) launches).
 void launch_slab_flush(const SlabFlushEntry* entries, int count, hipStream_t stream);
 
+// nn.Linear on the split-bf16 MFMA (linear.hip): C[M][N] = sum_k A(m, k) B(n, k), row-major,
+// at the level of conv_precision_level().  pass 0 forward (A = x[M][K], B = w[N][K], bias[N]
+// or null), 1 backward-data (A = dy[M][K], B = w[K][N]), 2 weight gradient (A = dy[K][M],
+// B = x[K][N]; accumulate: C += the product).  Every extent >= 1; operands and C below
+// 2 GiB.  A plan with splits > 1 needs `ws` of linear_workspace floats (the splits' partial
+// tiles, summed in order by a second launch that applies bias / accumulate).
+struct LinearPlan {
+  int tile;     // 64 or 128
+  int splits;   // reduction splits (grid.z)
+  int k_chunk;  // k per split, whole stages of 32
+};
+LinearPlan linear_plan(int M, int N, int K);  // the host rule, or linear_force_plan's choice
+int64_t linear_workspace(int M, int N, const LinearPlan& plan);
+void launch_linear_gemm(int pass, const float* a, const float* b, const float* bias, float* out,
+                        int M, int N, int K, const LinearPlan& plan, bool accumulate, float* ws,
+                        hipStream_t stream);
+// db[o] (+)= sum_r dy[r][o], fixed-order f32.
+void launch_linear_bias_grad(const float* dy, float* db, int R, int O, bool accumulate,
+                             hipStream_t stream);
+// Test / profiling hook: every Linear launch on the `tile` (64 / 128) and with `splits`
+// reduction splits (capped at the stages of the reduction); -1 = the host rule.
+void linear_force_plan(int tile, int splits);
+
 // (mean, M2) partials of z[n][c][s] per (image, channel): part_*[n][c] (width s).
 void launch_bn_stats(const float* z, float* part_mean, float* part_m2, int64_t n, int64_t c,
                      int64_t s, hipStream_t stream);

@@ -12,6 +12,7 @@ from typing import List, Union
 from torch import nn
 
 from torchgpipe_amd.ops.dropout import Dropout
+from torchgpipe_amd.ops.linear import NativeLinear
 
 __all__ = ['vgg16', 'VGG16_CONFIG']
 
@@ -21,8 +22,10 @@ VGG16_CONFIG: List[Union[int, str]] = [64, 64, 'M', 128, 128, 'M', 256, 256, 256
 
 
 def vgg16(num_classes: int = 1000, inplace: bool = False, batch_norm: bool = False,
-          dropout: float = 0.5) -> nn.Sequential:
-    """VGG-16 (configuration D); ``batch_norm`` adds a BatchNorm2d after each convolution."""
+          dropout: float = 0.5, native_linear: bool = False) -> nn.Sequential:
+    """VGG-16 (configuration D); ``batch_norm`` adds a BatchNorm2d after each convolution;
+    ``native_linear`` builds the classifier from ``ops.linear.NativeLinear`` (the split-bf16
+    dense GEMM; same parameters and state-dict keys)."""
     layers: List[nn.Module] = []
     channels = 3
     for v in VGG16_CONFIG:
@@ -37,9 +40,10 @@ def vgg16(num_classes: int = 1000, inplace: bool = False, batch_norm: bool = Fal
         channels = v
     layers.append(nn.Sequential(nn.AdaptiveAvgPool2d((7, 7)), nn.Flatten()))
     width = 4096
-    layers += [nn.Linear(channels * 7 * 7, width), nn.ReLU(inplace=inplace), Dropout(dropout),
-               nn.Linear(width, width), nn.ReLU(inplace=inplace), Dropout(dropout),
-               nn.Linear(width, num_classes)]
+    linear = NativeLinear if native_linear else nn.Linear
+    layers += [linear(channels * 7 * 7, width), nn.ReLU(inplace=inplace), Dropout(dropout),
+               linear(width, width), nn.ReLU(inplace=inplace), Dropout(dropout),
+               linear(width, num_classes)]
     model = nn.Sequential(*layers)
     for m in model.modules():
         if isinstance(m, nn.Conv2d):

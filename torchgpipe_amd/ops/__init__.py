@@ -6,9 +6,10 @@
 * :mod:`.philox` — bit-exact CPU reference of the Philox stream
 * :mod:`.misc` — spin kernel (race tests), multi-tensor pack/unpack
 * :mod:`.gradclip` — global-norm gradient clipping (fp64 sum of squares, in-place scale)
+* :mod:`.linear` — ``nn.Linear`` on the split-bf16 dense GEMM (``NativeLinear``, opt-in)
 """
-from torchgpipe_amd.ops import _ext, gradclip
+from torchgpipe_amd.ops import _ext, gradclip, linear
 
 available = _ext.available
 
-__all__ = ['available', 'gradclip']
+__all__ = ['available', 'gradclip', 'linear']

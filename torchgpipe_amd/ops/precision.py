@@ -6,6 +6,9 @@ on the bf16 matrix pipes: each operand is split exactly into three bf16 parts
 ``hi + mid + lo`` and a product is six partial products.  At the reduced levels the fused
 F(4x4) Winograd forward / backward-data of the 64-256-channel 3x3 layers runs on them too
 (``f4_conv_emu_kernel``, the three ``'high'`` products; ``ops.conv.f4_variant`` routes).
+The dense GEMMs of ``ops.linear.NativeLinear`` (``csrc/linear.hip``: forward, backward-data
+and weight gradient) are split-bf16 products too and follow the level; ``'medium'`` there
+really is ``hi*hi`` (there is no transform domain).
 The levels are those of :func:`torch.set_float32_matmul_precision`:
 
 ``'highest'`` (default)
@@ -30,14 +33,15 @@ not follow :func:`torch.get_float32_matmul_precision`.
 ``split_bf16`` and the ``reference_*`` functions are the fp64 oracle of these semantics.
 """
 import contextlib
-from typing import Iterator, Sequence, Tuple, Union
+from typing import Iterator, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
 import torch.nn.functional as F
 
 __all__ = ['LEVELS', 'set_conv_precision', 'get_conv_precision', 'conv_precision',
-           'autocast_lowp', 'split_bf16', 'reference_conv2d', 'reference_conv2d_backward']
+           'autocast_lowp', 'split_bf16', 'reference_conv2d', 'reference_conv2d_backward',
+           'reference_linear', 'reference_linear_backward']
 
 LEVELS = ('highest', 'high', 'medium')
 
@@ -153,3 +157,33 @@ def reference_conv2d_backward(dz: Tensor, x: Tensor, w: Tensor, stride: _Pair = 
     if relu:
         dx = dx * (x > 0).double()
     return dx, dw
+
+
+def _products(a: Tensor, b: Tensor, lv: int, mm) -> Tensor:
+    """fp64 ``mm(a, b)`` from the partial products of level ``lv`` of the fp32 ``a``, ``b``."""
+    if lv == 0:
+        return mm(a.double(), b.double())
+    ah, am, _ = split_bf16(a)
+    bh, bm, _ = split_bf16(b)
+    if lv == 2:
+        return mm(ah.double(), bh.double())
+    return mm(ah.double(), bh.double() + bm.double()) + mm(am.double(), bh.double())
+
+
+def reference_linear(x: Tensor, w: Tensor, b: Optional[Tensor] = None,
+                     level: str = 'highest') -> Tensor:
+    """fp64 ``F.linear(x, w, b)`` with the partial products of ``level``."""
+    y = _products(x.detach(), w.detach(), _index(level), lambda p, q: p.matmul(q.t()))
+    return y if b is None else y + b.detach().double()
+
+
+def reference_linear_backward(dy: Tensor, x: Tensor, w: Tensor,
+                              level: str = 'highest') -> Tuple[Tensor, Tensor, Tensor]:
+    """fp64 ``(dx, dw, db)`` of ``F.linear(x, w, b)`` for the output gradient ``dy``: dX from
+    the parts of dY and W, dW from the parts of dY and X, dB exact."""
+    lv = _index(level)
+    dy, x, w = dy.detach(), x.detach(), w.detach()
+    dy2, x2 = dy.reshape(-1, dy.shape[-1]), x.reshape(-1, x.shape[-1])
+    dx = _products(dy, w, lv, lambda p, q: p.matmul(q))
+    dw = _products(dy2, x2, lv, lambda p, q: p.t().mm(q))
+    return dx, dw, dy2.double().sum(0)
