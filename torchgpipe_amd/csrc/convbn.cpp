@@ -1952,6 +1952,79 @@ at::Tensor linear_bias_grad(const at::Tensor& dy, const c10::optional<at::Tensor
   return db;
 }
 
+// ---- fused attention, head dim 64 (attention.hip) ---------------------------------------------
+// q, k, v, do: [B, H, T, 64] views (last stride 1, the others multiples of 4 elements, 16-byte
+// aligned base, span below 2 GiB: a slice of a fused [B, T, 3, H, 64] projection is read in
+// place).  o and the gradients: [B, T, H, 64] memory returned as its [B, H, T, 64] view.
+
+AttnTensor attn_view(const at::Tensor& t, const char* name, const at::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on ", like.device());
+  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
+  TORCH_CHECK(t.dim() == 4 && t.sizes() == like.sizes() && t.size(3) == 64 && t.numel() > 0,
+              name, " must be a non-empty [B, H, T, 64] like q");
+  auto stride = [&](int d) { return t.size(d) == 1 ? int64_t{0} : t.stride(d); };
+  AttnTensor a{t.data_ptr<float>(), stride(0), stride(1), stride(2), 0};
+  TORCH_CHECK(t.stride(3) == 1 && a.sb % 4 == 0 && a.sh % 4 == 0 && a.st % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(a.p) % 16 == 0,
+              name, ": last stride 1, other strides multiples of 4, base 16-byte aligned");
+  a.bytes = ((t.size(0) - 1) * a.sb + (t.size(1) - 1) * a.sh + (t.size(2) - 1) * a.st + 64) * 4;
+  TORCH_CHECK(a.bytes <= kMaxBytes, name, " spans too much memory (< 2 GiB per tensor)");
+  return a;
+}
+
+at::Tensor attn_like(const at::Tensor& q) {  // [B, T, H, 64] memory, [B, H, T, 64] view
+  return at::empty({q.size(0), q.size(2), q.size(1), 64}, q.options()).transpose(1, 2);
+}
+
+std::tuple<at::Tensor, at::Tensor> attention_forward(const at::Tensor& q, const at::Tensor& k,
+                                                     const at::Tensor& v, bool causal,
+                                                     double scale) {
+  AttnArgs a{};
+  a.q = attn_view(q, "q", q);
+  a.k = attn_view(k, "k", q);
+  a.v = attn_view(v, "v", q);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  auto o = attn_like(q);
+  auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options());
+  a.o = o.data_ptr<float>();
+  a.lse = lse.data_ptr<float>();
+  a.B = static_cast<int>(q.size(0));
+  a.H = static_cast<int>(q.size(1));
+  a.T = static_cast<int>(q.size(2));
+  a.scale = static_cast<float>(scale);
+  launch_attention_forward(a, causal, cur_stream(q));
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> attention_backward(
+    const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& o, const at::Tensor& lse, bool causal, double scale) {
+  AttnArgs a{};
+  a.q = attn_view(q, "q", q);
+  a.k = attn_view(k, "k", q);
+  a.v = attn_view(v, "v", q);
+  a.dout = attn_view(dout, "do", q);
+  attn_view(o, "o", q);
+  TORCH_CHECK(o.transpose(1, 2).is_contiguous(), "o must be [B, T, H, 64] memory");
+  check_f32(lse, "lse", q);
+  TORCH_CHECK(lse.numel() == q.numel() / 64, "lse must be [B, H, T]");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+  auto dq = attn_like(q), dk = attn_like(q), dv = attn_like(q);
+  auto delta = at::empty_like(lse);
+  a.o = o.data_ptr<float>();
+  a.lse = lse.data_ptr<float>();
+  a.delta = delta.data_ptr<float>();
+  a.dq = dq.data_ptr<float>();
+  a.dk = dk.data_ptr<float>();
+  a.dv = dv.data_ptr<float>();
+  a.B = static_cast<int>(q.size(0));
+  a.H = static_cast<int>(q.size(1));
+  a.T = static_cast<int>(q.size(2));
+  a.scale = static_cast<float>(scale);
+  launch_attention_backward(a, causal, cur_stream(q));
+  return {dq, dk, dv};
+}
+
 }  // namespace
 }  // namespace tgpipe
 
@@ -2024,6 +2097,10 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
   m.def("linear_force_plan(int tile, int splits) -> ()", [](int64_t tile, int64_t splits) {
     tgpipe::linear_force_plan(static_cast<int>(tile), static_cast<int>(splits));
   });
+  m.def("attention_forward(Tensor q, Tensor k, Tensor v, bool causal, float scale) -> "
+        "(Tensor, Tensor)");
+  m.def("attention_backward(Tensor do, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, "
+        "bool causal, float scale) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
@@ -2043,6 +2120,8 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("linear_backward_data", &tgpipe::linear_backward_data);
   m.impl("linear_backward_weight", &tgpipe::linear_backward_weight);
   m.impl("linear_bias_grad", &tgpipe::linear_bias_grad);
+  m.impl("attention_forward", &tgpipe::attention_forward);
+  m.impl("attention_backward", &tgpipe::attention_backward);
   m.impl("bn_train_forward", &tgpipe::bn_train_forward);
   m.impl("bn_train_backward", &tgpipe::bn_train_backward);
   m.impl("dbn_commit64", &tgpipe::dbn_commit64);

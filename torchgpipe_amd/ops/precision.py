@@ -8,7 +8,9 @@ F(4x4) Winograd forward / backward-data of the 64-256-channel 3x3 layers runs on
 (``f4_conv_emu_kernel``, the three ``'high'`` products; ``ops.conv.f4_variant`` routes).
 The dense GEMMs of ``ops.linear.NativeLinear`` (``csrc/linear.hip``: forward, backward-data
 and weight gradient) are split-bf16 products too and follow the level; ``'medium'`` there
-really is ``hi*hi`` (there is no transform domain).
+really is ``hi*hi`` (there is no transform domain).  So are the GEMMs of the fused
+attention kernels (``ops.attention``, ``csrc/attention.hip``): ``Q K^T``, ``P V`` and the
+five products of the backward, with the fp32 ``P`` and ``dS`` split like any other operand.
 The levels are those of :func:`torch.set_float32_matmul_precision`:
 
 ``'highest'`` (default)
@@ -41,7 +43,8 @@ import torch.nn.functional as F
 
 __all__ = ['LEVELS', 'set_conv_precision', 'get_conv_precision', 'conv_precision',
            'autocast_lowp', 'split_bf16', 'reference_conv2d', 'reference_conv2d_backward',
-           'reference_linear', 'reference_linear_backward']
+           'reference_linear', 'reference_linear_backward', 'reference_attention',
+           'reference_attention_backward']
 
 LEVELS = ('highest', 'high', 'medium')
 
@@ -187,3 +190,59 @@ def reference_linear_backward(dy: Tensor, x: Tensor, w: Tensor,
     dx = _products(dy, w, lv, lambda p, q: p.matmul(q))
     dw = _products(dy2, x2, lv, lambda p, q: p.t().mm(q))
     return dx, dw, dy2.double().sum(0)
+
+
+def _scores(q: Tensor, k: Tensor, causal: bool, scale: Optional[float], lv: int) -> Tensor:
+    """fp64 ``scale * q k^T`` from the level's products, ``-inf`` above the diagonal."""
+    scale = q.shape[-1] ** -0.5 if scale is None else scale
+    s = scale * _products(q, k, lv, lambda a, b: a.matmul(b.transpose(-1, -2)))
+    if causal:
+        t = q.shape[-2]
+        s = s.masked_fill(torch.ones(t, t, dtype=torch.bool, device=q.device).triu(1),
+                          float('-inf'))
+    return s
+
+
+def _fp32(t: Tensor, lv: int) -> Tensor:
+    """What a kernel holds of the fp64 ``t`` before it splits it: the fp32 rounding (exact at
+    ``'highest'``)."""
+    return t if lv == 0 else t.float()
+
+
+def reference_attention(q: Tensor, k: Tensor, v: Tensor, causal: bool = False,
+                        scale: Optional[float] = None, level: str = 'highest') -> Tensor:
+    """fp64 ``softmax(scale * q k^T [+ causal mask]) v`` over ``[..., T, D]``.  At a reduced
+    level: the level's products of ``(q, k)``, the softmax in fp64, ``P = exp(S - max)``
+    rounded to fp32 and split, the level's products of ``(P, v)``, divided by the row sum of
+    the fp32 ``P``."""
+    lv = _index(level)
+    q, k, v = q.detach(), k.detach(), v.detach()
+    s = _scores(q, k, causal, scale, lv)
+    p = _fp32((s - s.amax(-1, keepdim=True)).exp(), lv)
+    return _products(p, v, lv, lambda a, b: a.matmul(b)) / p.double().sum(-1, keepdim=True)
+
+
+def reference_attention_backward(do: Tensor, q: Tensor, k: Tensor, v: Tensor,
+                                 causal: bool = False, scale: Optional[float] = None,
+                                 level: str = 'highest') -> Tuple[Tensor, Tensor, Tensor]:
+    """fp64 ``(dq, dk, dv)`` of :func:`reference_attention` for the output gradient ``do``,
+    as the kernels form them: ``P = softmax`` and ``dS = P (dP - rowsum(do * o))`` in fp64,
+    each rounded to fp32 and split at a reduced level; the level's products for ``S``,
+    ``dP = do v^T``, ``dv = P^T do``, ``dq = scale dS k`` and ``dk = scale dS^T q``."""
+    lv = _index(level)
+    do, q, k, v = do.detach(), q.detach(), k.detach(), v.detach()
+    sc = q.shape[-1] ** -0.5 if scale is None else scale
+
+    def mm(a: Tensor, b: Tensor) -> Tensor:
+        return a.matmul(b)
+
+    def mm_t(a: Tensor, b: Tensor) -> Tensor:  # the reduction over a's rows
+        return a.transpose(-1, -2).matmul(b)
+
+    o = reference_attention(q, k, v, causal, scale, level)
+    p = _fp32(_scores(q, k, causal, scale, lv).softmax(-1), lv)
+    delta = (do.double() * o).sum(-1, keepdim=True)
+    dp = _products(do, v, lv, lambda a, b: a.matmul(b.transpose(-1, -2)))
+    ds = _fp32(p.double() * (dp - delta), lv)
+    return (sc * _products(ds, k, lv, mm), sc * _products(ds, q, lv, mm_t),
+            _products(p, do, lv, mm_t))
