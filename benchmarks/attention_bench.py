@@ -1,8 +1,10 @@
-"""Fused fp32 attention (``csrc/attention.hip``) at each precision level against
-``F.scaled_dot_product_attention`` on the same fp32 tensors, forward and backward.
+"""Fused fp32 attention (``csrc/attention.hip``, ``csrc/attention128.hip``) at each precision
+level against ``F.scaled_dot_product_attention`` on the same fp32 tensors, forward and
+backward.
 
-Grid: ``B * H`` in {16, 96} (B = 1), ``T`` in {512, 2048, 8192}, head dim 64, causal and not.
-Both implementations get the same contiguous ``[1, H, T, 64]`` inputs in one process and
+Grid: ``B * H`` in {16, 96} (B = 1), ``T`` in {512, 2048, 8192}, head dim 64 or, with
+``--head-dim 128``, 128, causal and not.
+Both implementations get the same contiguous ``[1, H, T, D]`` inputs in one process and
 alternate window by window; a window is ``calls`` back-to-back calls between two device events
 (20 / 5 / 1 calls by ``T``), each figure the median over ``--windows`` windows with the
 min-max spread beside it.  The library's forward runs with autograd recording, as in
@@ -10,7 +12,8 @@ training (it keeps its ``T x T`` tensors for the backward).  The backward rows t
 backward alone: the native ``attention_backward`` op on the forward's saved ``o`` and
 ``lse``, the library's autograd over a retained graph.  ``peak_mb`` is the allocator's peak
 over one forward plus backward, above what the inputs hold.  ``t_mfma_us`` = the pass's GEMM
-units (2 forward, 7 native backward, 5 library backward; half of each when causal) times the
+units (2 forward, 7 native backward -- 8 at head dim 128, where dV and dK are two kernels --,
+5 library backward; half of each when causal) times the
 level's bf16 products over the 2.5 PFLOP/s dense bf16 rate (library: over its 157 TFLOP/s
 fp32 matrix rate); ``share`` is it over the time.
 
@@ -41,17 +44,19 @@ def main() -> None:
     p.add_argument('--lengths', default='512,2048,8192')
     p.add_argument('--windows', type=int, default=5)
     p.add_argument('--warmup', type=int, default=1)
+    p.add_argument('--head-dim', type=int, default=64, choices=(64, 128))
     p.add_argument('--out', default=None)
     a = p.parse_args()
     if not _ext.available():
         raise RuntimeError(f'HIP extension not loadable: {_ext.load_error()!r}')
     ops = torch.ops.tgpipe
+    d, scale = a.head_dim, a.head_dim ** -0.5
     dev = torch.device('cuda', 0)
     rows: List[Dict[str, object]] = []
     for h in map(int, a.heads.split(',')):
         for t in map(int, a.lengths.split(',')):
             gen = torch.Generator(device=dev).manual_seed(0)
-            q, k, v, do = (torch.randn(1, h, t, 64, device=dev, generator=gen) for _ in range(4))
+            q, k, v, do = (torch.randn(1, h, t, d, device=dev, generator=gen) for _ in range(4))
             leaves = [x.requires_grad_() for x in (q, k, v)]
             calls = CALLS.get(t, 1)
             for causal in (False, True):
@@ -83,12 +88,12 @@ def main() -> None:
                     with precision.conv_precision(level):
                         peaks[f'native_{level}'] = peak(lambda: native_attention(q, k, v, causal))
                         o, lse = ops.attention_forward(q.detach(), k.detach(), v.detach(), causal,
-                                                       0.125)
+                                                       scale)
                     impls[f'native_{level}'] = {
                         'forward': at(lambda: ops.attention_forward(q.detach(), k.detach(),
-                                                                    v.detach(), causal, 0.125)),
+                                                                    v.detach(), causal, scale)),
                         'backward': at(lambda o=o, lse=lse: ops.attention_backward(
-                            do, q.detach(), k.detach(), v.detach(), o, lse, causal, 0.125))}
+                            do, q.detach(), k.detach(), v.detach(), o, lse, causal, scale))}
                 for pass_name in ('forward', 'backward'):
                     times: Dict[str, List[float]] = {impl: [] for impl in impls}
                     for i in range(a.warmup + a.windows):
@@ -97,11 +102,12 @@ def main() -> None:
                             if i >= a.warmup:
                                 times[impl].append(ms)
                     lib_ms = statistics.median(times['library'])
-                    unit = 2 * h * t * t * 64 * (0.5 if causal else 1.0)  # FLOPs of one GEMM
+                    unit = 2 * h * t * t * d * (0.5 if causal else 1.0)  # FLOPs of one GEMM
                     for impl, ts in times.items():
                         med = statistics.median(ts)
                         native = impl != 'library'
-                        units = 2 if pass_name == 'forward' else (7 if native else 5)
+                        bwd_units = (7 if d == 64 else 8) if native else 5
+                        units = 2 if pass_name == 'forward' else bwd_units
                         t_mfma = (units * unit * PRODUCTS[impl[len('native_'):]] / BF16_RATE
                                   if native else units * unit / F32_RATE)
                         row = {'BH': h, 'T': t, 'causal': causal, 'pass': pass_name, 'impl': impl,

@@ -28,14 +28,15 @@ ROCM = os.environ.get('ROCM_PATH', '/opt/rocm')
 
 KERNEL_SOURCES = ['kernels.hip', 'winograd.hip', 'winograd_f4.hip', 'conv_gemm.hip',
                   'batchnorm.hip', 'pool.hip', 'unet_ops.hip', 'gradclip.hip', 'wire.hip',
-                  'optim.hip', 'linear.hip', 'attention.hip']
+                  'optim.hip', 'linear.hip', 'attention.hip', 'attention128.hip']
 # extra hipcc flags per kernel source.  linear.hip: no packed-f32 VALU forms (v_pk_*_f32) for
 # its float4 epilogue adds -- plain f32 adds, rounded as the scalar path rounds them;
-# attention.hip: the same for its softmax and rescale arithmetic
+# attention.hip, attention128.hip: the same for their softmax and rescale arithmetic
 _NO_PK_F32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-KERNEL_FLAGS = {'linear.hip': _NO_PK_F32, 'attention.hip': _NO_PK_F32}
+KERNEL_FLAGS = {'linear.hip': _NO_PK_F32, 'attention.hip': _NO_PK_F32,
+                'attention128.hip': _NO_PK_F32}
 HOST_SOURCES = ['bindings.cpp', 'convbn.cpp']
-HEADERS = ['kernels.h', 'philox.h', 'bf16_round.h']
+HEADERS = ['kernels.h', 'philox.h', 'bf16_round.h', 'attention_common.h']
 HOST_HEADERS = ['aten_checks.h']  # ATen-side helpers: the host sources only
 
 

@@ -1952,28 +1952,38 @@ at::Tensor linear_bias_grad(const at::Tensor& dy, const c10::optional<at::Tensor
   return db;
 }
 
-// ---- fused attention, head dim 64 (attention.hip) ---------------------------------------------
-// q, k, v, do: [B, H, T, 64] views (last stride 1, the others multiples of 4 elements, 16-byte
-// aligned base, span below 2 GiB: a slice of a fused [B, T, 3, H, 64] projection is read in
-// place).  o and the gradients: [B, T, H, 64] memory returned as its [B, H, T, 64] view.
+// ---- fused attention, head dim 64 (attention.hip) or 128 (attention128.hip) -------------------
+// q, k, v, do: [B, H, T, D] views (last stride 1, the others multiples of 4 elements, 16-byte
+// aligned base, span below 2 GiB: a slice of a fused [B, T, 3, H, D] projection is read in
+// place).  o and the gradients: [B, T, H, D] memory returned as its [B, H, T, D] view.
 
 AttnTensor attn_view(const at::Tensor& t, const char* name, const at::Tensor& like) {
   TORCH_CHECK(t.is_cuda() && t.device() == like.device(), name, " must be on ", like.device());
   TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-  TORCH_CHECK(t.dim() == 4 && t.sizes() == like.sizes() && t.size(3) == 64 && t.numel() > 0,
-              name, " must be a non-empty [B, H, T, 64] like q");
+  TORCH_CHECK(t.dim() == 4 && t.sizes() == like.sizes() &&
+                  (t.size(3) == 64 || t.size(3) == 128) && t.numel() > 0,
+              name, " must be a non-empty [B, H, T, 64 or 128] like q");
   auto stride = [&](int d) { return t.size(d) == 1 ? int64_t{0} : t.stride(d); };
   AttnTensor a{t.data_ptr<float>(), stride(0), stride(1), stride(2), 0};
   TORCH_CHECK(t.stride(3) == 1 && a.sb % 4 == 0 && a.sh % 4 == 0 && a.st % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(a.p) % 16 == 0,
               name, ": last stride 1, other strides multiples of 4, base 16-byte aligned");
-  a.bytes = ((t.size(0) - 1) * a.sb + (t.size(1) - 1) * a.sh + (t.size(2) - 1) * a.st + 64) * 4;
+  a.bytes = ((t.size(0) - 1) * a.sb + (t.size(1) - 1) * a.sh + (t.size(2) - 1) * a.st +
+             t.size(3)) * 4;
   TORCH_CHECK(a.bytes <= kMaxBytes, name, " spans too much memory (< 2 GiB per tensor)");
   return a;
 }
 
-at::Tensor attn_like(const at::Tensor& q) {  // [B, T, H, 64] memory, [B, H, T, 64] view
-  return at::empty({q.size(0), q.size(2), q.size(1), 64}, q.options()).transpose(1, 2);
+at::Tensor attn_like(const at::Tensor& q) {  // [B, T, H, D] memory, [B, H, T, D] view
+  return at::empty({q.size(0), q.size(2), q.size(1), q.size(3)}, q.options()).transpose(1, 2);
+}
+
+void attn_sizes(AttnArgs& a, const at::Tensor& q, double scale) {
+  a.B = static_cast<int>(q.size(0));
+  a.H = static_cast<int>(q.size(1));
+  a.T = static_cast<int>(q.size(2));
+  a.D = static_cast<int>(q.size(3));
+  a.scale = static_cast<float>(scale);
 }
 
 std::tuple<at::Tensor, at::Tensor> attention_forward(const at::Tensor& q, const at::Tensor& k,
@@ -1988,10 +1998,7 @@ std::tuple<at::Tensor, at::Tensor> attention_forward(const at::Tensor& q, const 
   auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options());
   a.o = o.data_ptr<float>();
   a.lse = lse.data_ptr<float>();
-  a.B = static_cast<int>(q.size(0));
-  a.H = static_cast<int>(q.size(1));
-  a.T = static_cast<int>(q.size(2));
-  a.scale = static_cast<float>(scale);
+  attn_sizes(a, q, scale);
   launch_attention_forward(a, causal, cur_stream(q));
   return {o, lse};
 }
@@ -2005,9 +2012,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attention_backward(
   a.v = attn_view(v, "v", q);
   a.dout = attn_view(dout, "do", q);
   attn_view(o, "o", q);
-  TORCH_CHECK(o.transpose(1, 2).is_contiguous(), "o must be [B, T, H, 64] memory");
+  TORCH_CHECK(o.transpose(1, 2).is_contiguous(), "o must be [B, T, H, D] memory");
   check_f32(lse, "lse", q);
-  TORCH_CHECK(lse.numel() == q.numel() / 64, "lse must be [B, H, T]");
+  TORCH_CHECK(lse.numel() == q.numel() / q.size(3), "lse must be [B, H, T]");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
   auto dq = attn_like(q), dk = attn_like(q), dv = attn_like(q);
   auto delta = at::empty_like(lse);
@@ -2017,10 +2024,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attention_backward(
   a.dq = dq.data_ptr<float>();
   a.dk = dk.data_ptr<float>();
   a.dv = dv.data_ptr<float>();
-  a.B = static_cast<int>(q.size(0));
-  a.H = static_cast<int>(q.size(1));
-  a.T = static_cast<int>(q.size(2));
-  a.scale = static_cast<float>(scale);
+  attn_sizes(a, q, scale);
   launch_attention_backward(a, causal, cur_stream(q));
   return {dq, dk, dv};
 }

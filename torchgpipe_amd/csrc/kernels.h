@@ -399,10 +399,11 @@ void launch_linear_bias_grad(const float* dy, float* db, int R, int O, bool accu
 // reduction splits (capped at the stages of the reduction); -1 = the host rule.
 void linear_force_plan(int tile, int splits);
 
-// Fused fp32 attention, head dim 64, on the split-bf16 MFMA (attention.hip), at the level of
-// conv_precision_level().  q, k, v, dout: logical [B, H, T, 64] views, element strides sb /
-// sh / st (last stride 1), each a multiple of 4, 16-byte aligned base, `bytes` the view's span
-// from `p` (< 2 GiB).  o, dq, dk, dv: [B, T, H, 64] memory; lse, delta: [B, H, T].
+// Fused fp32 attention, head dim D = 64 (attention.hip) or 128 (attention128.hip), on the
+// split-bf16 MFMA, at the level of conv_precision_level().  q, k, v, dout: logical
+// [B, H, T, D] views, element strides sb / sh / st (last stride 1), each a multiple of 4,
+// 16-byte aligned base, `bytes` the view's span from `p` (< 2 GiB).  o, dq, dk, dv:
+// [B, T, H, D] memory; lse, delta: [B, H, T].
 struct AttnTensor {
   const float* p;
   int64_t sb, sh, st, bytes;
@@ -414,10 +415,12 @@ struct AttnArgs {
   float* delta;              // backward scratch, rowsum(dout . o)
   float *dq, *dk, *dv;
   int B, H, T;
+  int D;  // head dim: the launchers dispatch on it
   float scale;
 };
 void launch_attention_forward(const AttnArgs& args, bool causal, hipStream_t stream);
-// delta, then dK / dV (a workgroup per key block), then dQ (a workgroup per query block)
+// delta, then the key-owning pass (a workgroup per key block: dK / dV in one kernel at D = 64,
+// dV and dK kernels at D = 128), then dQ (a workgroup per query block)
 void launch_attention_backward(const AttnArgs& args, bool causal, hipStream_t stream);
 
 // (mean, M2) partials of z[n][c][s] per (image, channel): part_*[n][c] (width s).

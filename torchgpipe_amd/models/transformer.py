@@ -2,8 +2,8 @@
 
 Pre-LayerNorm blocks of causal self-attention
 (:class:`~torchgpipe_amd.ops.attention.NativeSelfAttention`: the fused fp32 attention kernels
-when the head dim is 64) and a GELU MLP.  Every layer maps one tensor to one tensor, so any
-``balance`` over the ``2 * layers + 2`` children is a valid partition.
+when the head dim is 64 or 128) and a GELU MLP.  Every layer maps one tensor to one tensor, so
+any ``balance`` over the ``2 * layers + 2`` children is a valid partition.
 """
 from torch import Tensor, nn
 import torch
@@ -72,8 +72,8 @@ def transformer_lm(vocab: int = 32000, d_model: int = 768, heads: int = 12, laye
     """Embedding, ``layers`` x (attention block, MLP block), head: ``2 * layers + 2`` children
     mapping int64 ``tokens [B, T <= seq_len]`` to logits ``[B, T, vocab]``.
 
-    ``d_model == 64 * heads`` puts the attention on the native kernels; ``native_linear``
-    builds every projection from ``ops.linear.NativeLinear``."""
+    ``d_model == 64 * heads`` or ``128 * heads`` puts the attention on the native kernels;
+    ``native_linear`` builds every projection from ``ops.linear.NativeLinear``."""
     blocks = [Embedding(vocab, d_model, seq_len)]
     for _ in range(layers):
         blocks.append(AttentionBlock(d_model, heads, native_linear))

@@ -7,7 +7,8 @@
 * :mod:`.misc` — spin kernel (race tests), multi-tensor pack/unpack
 * :mod:`.gradclip` — global-norm gradient clipping (fp64 sum of squares, in-place scale)
 * :mod:`.linear` — ``nn.Linear`` on the split-bf16 dense GEMM (``NativeLinear``, opt-in)
-* :mod:`.attention` — fused fp32 attention, head dim 64, split-bf16 (``NativeSelfAttention``)
+* :mod:`.attention` — fused fp32 attention, head dims 64 / 128, split-bf16
+  (``NativeSelfAttention``)
 """
 from torchgpipe_amd.ops import _ext, gradclip, linear
 

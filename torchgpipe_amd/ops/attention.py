@@ -1,4 +1,5 @@
-"""Fused fp32 scaled-dot-product attention for head dim 64 (``csrc/attention.hip``), opt-in.
+"""Fused fp32 scaled-dot-product attention for head dims 64 and 128 (``csrc/attention.hip``,
+``csrc/attention128.hip``), opt-in.
 
 ``softmax(scale * q k^T [+ causal mask]) v`` without the ``T x T`` score matrix in memory,
 forward and backward, as split-bf16 partial products on ``v_mfma_f32_32x32x16_bf16`` with
@@ -24,28 +25,29 @@ from torchgpipe_amd.ops import _ext
 from torchgpipe_amd.ops.linear import NativeLinear
 from torchgpipe_amd.ops.precision import autocast_lowp
 
-__all__ = ['native_attention', 'NativeSelfAttention', 'eligible', 'HEAD_DIM']
+__all__ = ['native_attention', 'NativeSelfAttention', 'eligible', 'HEAD_DIM', 'HEAD_DIMS']
 
-HEAD_DIM = 64
+HEAD_DIM = 64          # the first head dim the kernels had; kept for its importers
+HEAD_DIMS = (64, 128)  # every head dim with kernels
 _MAX_BYTES = 0x7ffffff0  # buffer-resource offsets: every view spans less than 2 GiB
 
 
 def _readable(t: Tensor) -> bool:
-    """The kernels' stride rules for one ``[B, H, T, 64]`` view."""
+    """The kernels' stride rules for one ``[B, H, T, D]`` view."""
     strides = [0 if n == 1 else s for n, s in zip(t.shape[:3], t.stride()[:3])]
-    span = sum((n - 1) * s for n, s in zip(t.shape[:3], strides)) + HEAD_DIM
+    span = sum((n - 1) * s for n, s in zip(t.shape[:3], strides)) + t.shape[3]
     return (t.stride(3) == 1 and all(s % 4 == 0 for s in strides)
             and t.data_ptr() % 16 == 0 and 4 * span <= _MAX_BYTES)
 
 
 def eligible(q: Tensor, k: Tensor, v: Tensor) -> bool:
     """Whether the native kernels take this call: fp32 GPU tensors on one device of one shape
-    ``[B, H, T, 64]`` with ``T >= 1``, last stride 1, the other strides multiples of 4
-    elements, 16-byte aligned, each view spanning less than 2 GiB."""
+    ``[B, H, T, D]`` with ``D`` in :data:`HEAD_DIMS` and ``T >= 1``, last stride 1, the other
+    strides multiples of 4 elements, 16-byte aligned, each view spanning less than 2 GiB."""
     if not all(t.is_cuda and t.dtype == torch.float32 and t.device == q.device
                and t.shape == q.shape for t in (q, k, v)):
         return False
-    if q.dim() != 4 or q.shape[3] != HEAD_DIM or q.numel() == 0:
+    if q.dim() != 4 or q.shape[3] not in HEAD_DIMS or q.numel() == 0:
         return False
     return all(_readable(t) for t in (q, k, v))
 
@@ -73,12 +75,13 @@ class _NativeAttention(torch.autograd.Function):
 def native_attention(q: Tensor, k: Tensor, v: Tensor, causal: bool = False,
                      scale: Optional[float] = None) -> Tensor:
     """``F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)`` on the native
-    kernels (see :func:`eligible`; anything else raises).  The result is ``[B, T, H, 64]``
-    memory viewed as ``[B, H, T, 64]``, and so are the gradients."""
+    kernels (see :func:`eligible`; anything else raises).  ``scale`` defaults to
+    ``1 / sqrt(D)``.  The result is ``[B, T, H, D]`` memory viewed as ``[B, H, T, D]``, and so
+    are the gradients."""
     if not eligible(q, k, v):
-        raise ValueError('native_attention needs fp32 GPU tensors [B, H, T, 64] of one shape '
-                         'with last stride 1 and 16-byte aligned rows')
-    scale = 1.0 / math.sqrt(HEAD_DIM) if scale is None else float(scale)
+        raise ValueError('native_attention needs fp32 GPU tensors [B, H, T, 64 or 128] of one '
+                         'shape with last stride 1 and 16-byte aligned rows')
+    scale = 1.0 / math.sqrt(q.shape[3]) if scale is None else float(scale)
     return _NativeAttention.apply(q, k, v, bool(causal), scale)
 
 
@@ -86,8 +89,8 @@ class NativeSelfAttention(nn.Module):
     """Multi-head self-attention over ``x [B, T, embed_dim]``: one fused projection ``qkv``,
     attention per head, the output projection ``proj``.
 
-    With head dim 64 a GPU fp32 call runs the native kernels: they read q, k, v as slices of
-    the ``[B, T, 3, H, 64]`` projection output and write ``[B, T, H, 64]``, which ``proj``
+    With head dim 64 or 128 a GPU fp32 call runs the native kernels: they read q, k, v as slices
+    of the ``[B, T, 3, H, D]`` projection output and write ``[B, T, H, D]``, which ``proj``
     reads as it is -- no transpose copies.  CPU tensors, ``torch.autocast`` to a lower
     precision, other head dims and ineligible strides run
     ``F.scaled_dot_product_attention`` on the same parameters.  ``native_linear`` builds the
