@@ -548,7 +548,7 @@ at::Tensor wino4_conv(const at::Tensor& x_in, const at::Tensor& u,
   auto y = at::empty({n, out_channels, h, w}, x.options());
   if (y.numel() == 0) return y;
   TORCH_CHECK(variant == -1 || wino4_variant_known(static_cast<int>(variant)),
-              "variant must be -1, 4-10, 12, 14-18, 20-22 or 24");
+              "variant must be -1, 4-10, 12, 14-18, 20-22, 24 or 25");
   const WinoPlan plan = wino4_plan(n, r, h, w, out_channels, static_cast<int>(variant),
                                    static_cast<int>(splits));
   at::Tensor ws;
@@ -627,9 +627,9 @@ at::Tensor wino4_wgrad(const at::Tensor& x_in, const at::Tensor& dy_in, int64_t 
   TORCH_CHECK(wino4_wgrad_supported(n, c, k, h, w),
               "input too large for the F(4x4) weight-gradient kernel (needs < 1 GiB); "
               "use wino_wgrad");
-  TORCH_CHECK(variant >= 0 && variant <= 3,
-              "variant must be 0 (fused), 1 (non-fused), 2 (split-bf16 batched GEMM) or 3 (fused, "
-              "x rows through LDS)");
+  TORCH_CHECK(variant >= 0 && variant <= 4,
+              "variant must be 0 (fused), 1 (non-fused), 2 (split-bf16 batched GEMM), 3 (fused, "
+              "x rows through LDS) or 4 (3 with the serial step)");
   const WinoPlan plan = wino4_wgrad_plan(n, c, k, h, w, static_cast<int>(variant),
                                          static_cast<int>(splits));
   at::Tensor ws;

@@ -153,7 +153,7 @@ void launch_wino_conv(const float* x, const float* u, const float* bias, float* 
 
 // Winograd F(4x4,3x3) (winograd_f4.hip): same convolution, 36 MFMA multiplies per 16
 // output pixels.  Transformed weights U4[Rp4/4][Op4/16][4][16][36] (Rp4 = multiple of 4,
-// Op4 = multiple of 64).  The variants (4-10, 12, 14-18, 20-22, 24) are the rows of
+// Op4 = multiple of 64).  The variants (4-10, 12, 14-18, 20-22, 24, 25) are the rows of
 // winograd_f4.hip's kF4Variants, described in that file's header comment.  wino4_plan
 // resolves the id that runs (an unknown id or -1: 5; a row-staged variant whose width
 // precondition fails: its fallback), the split-K count and the workspace, which for the
@@ -216,8 +216,9 @@ void launch_bg_conv(const float* x, const float* a, const float* bias, float* y,
 // 16 output pixels of each (k, c) pair; 64 k x 32 c per 8-wave workgroup, tiles split
 // over `splits` workgroups.  variant 0: fused (patch / gradient-tile staging inside the
 // GEMM kernel); 1: non-fused (transform passes into the GEMM's LDS image order, then an
-// LDS-DMA GEMM); 2: the split-bf16 batched GEMM; 3: 0 with the x rows staged through LDS.
-// wino4_wgrad_plan resolves the variant that runs (3 becomes 0 unless W % 4 == 0 and
+// LDS-DMA GEMM); 2: the split-bf16 batched GEMM; 3: 0 with the x rows staged through LDS;
+// 4: 3 with the serial step (the A/B arm of 3, planned as 3).
+// wino4_wgrad_plan resolves the variant that runs (3 / 4 become 0 unless W % 4 == 0 and
 // W >= 16), the split count (`splits` > 0, else each variant's model; every split owns
 // >= 1 step) and the workspace: the split-K partials and the transformed operands of 1 / 2.
 bool wino4_wgrad_supported(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w);

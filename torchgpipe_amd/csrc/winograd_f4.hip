@@ -38,6 +38,7 @@
 //   18       6 with the weight slab two steps ahead in a three-image LDS ring
 //            (f4_conv_ring_kernel; TGPIPE_F4_FUSED_VARIANT=18)
 //   20-22    timing ablations of 16 (wrong results; W % 4 == 0 and W >= 24, else run as 6)
+//   25       16 under a second id (A/B arm; profiles/KERNELS.md "Round 19")
 //   24       fused, on the bf16 matrix pipes: the three `high` partial products of split-bf16
 //            U and V (f4_conv_emu_kernel; its own weight image, launch_wino4_emu_weight;
 //            16-channel chunks)        <- conv precision high / medium, 64-256 output channels
@@ -47,7 +48,10 @@
 //    1       non-fused: f4_wg_vx / f4_wg_mdy transform passes, then f4_wgrad_gemm_kernel
 //    2       split-bf16 batched GEMM (wg_*_emu transform passes, bg_gemm_emu_kernel)
 //    3       0 with the x rows staged through LDS, f4_wgrad_rows_kernel (W % 4 == 0 and
-//            W >= 16, else runs as 0)
+//            W >= 16, else runs as 0); its step is pipelined (f4_pipe_step): the transforms and
+//            ring reads issue between the MFMAs of the step
+//    4       3 with the serial step (transform, ring reads, MFMAs one after the other): the
+//            A/B arm and bit-for-bit reference of 3
 //
 // Padding taps (image borders, tiles past the end) are raw buffer loads with an
 // out-of-range offset: the hardware returns 0, so no select sits between a load and
@@ -217,32 +221,38 @@ __device__ __forceinline__ void f4_load_patch(F4Patch& p, __amdgpu_buffer_rsrc_t
 // column pass on adjacent column pairs, the row pass on adjacent row pairs -- with the
 // packed fp32 VALU: 148 instead of 242 VALU instructions per patch (the patch waves'
 // VALU work is what their SIMDs stall on, profiles/pmc_f4_kernels.json valu_per_mfma).
+// Column pass of pair jp (columns 2jp, 2jp+1) and row pass of pair ip (rows 2ip, 2ip+1): the
+// six independent slices of the transform, which the pipelined steps (f4_pipe_step) place
+// between MFMA quads.
+__device__ __forceinline__ void f4_transform_cols(float* d, int jp) {
+  floatx2 c[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) c[i] = floatx2{d[i * 6 + 2 * jp], d[i * 6 + 2 * jp + 1]};
+  bt6(c[0], c[1], c[2], c[3], c[4], c[5]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    d[i * 6 + 2 * jp] = c[i][0];
+    d[i * 6 + 2 * jp + 1] = c[i][1];
+  }
+}
+
+__device__ __forceinline__ void f4_transform_rows(float* d, int ip) {
+  floatx2 r[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) r[j] = floatx2{d[2 * ip * 6 + j], d[(2 * ip + 1) * 6 + j]};
+  bt6(r[0], r[1], r[2], r[3], r[4], r[5]);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    d[2 * ip * 6 + j] = r[j][0];
+    d[(2 * ip + 1) * 6 + j] = r[j][1];
+  }
+}
+
 __device__ __forceinline__ void f4_transform(F4Patch& p) {
-  float* d = p.d;
 #pragma unroll
-  for (int jp = 0; jp < 3; ++jp) {
-    floatx2 c[6];
+  for (int jp = 0; jp < 3; ++jp) f4_transform_cols(p.d, jp);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) c[i] = floatx2{d[i * 6 + 2 * jp], d[i * 6 + 2 * jp + 1]};
-    bt6(c[0], c[1], c[2], c[3], c[4], c[5]);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      d[i * 6 + 2 * jp] = c[i][0];
-      d[i * 6 + 2 * jp + 1] = c[i][1];
-    }
-  }
-#pragma unroll
-  for (int ip = 0; ip < 3; ++ip) {
-    floatx2 r[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) r[j] = floatx2{d[2 * ip * 6 + j], d[(2 * ip + 1) * 6 + j]};
-    bt6(r[0], r[1], r[2], r[3], r[4], r[5]);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      d[2 * ip * 6 + j] = r[j][0];
-      d[(2 * ip + 1) * 6 + j] = r[j][1];
-    }
-  }
+  for (int ip = 0; ip < 3; ++ip) f4_transform_rows(p.d, ip);
 }
 
 __device__ __forceinline__ void f4_transform_store(F4Patch& p, float* vdst) {
@@ -341,6 +351,105 @@ __device__ __forceinline__ void f4_mfma_ahead(floatx4 (&acc)[kP], const float* b
     if (q + kAhead < kQ) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
   }
+}
+
+// ---- pipelined step of the row-staged fused weight gradient (f4_wgrad_rows_kernel<1>) -----
+// The 36 MFMAs of a step as nine chunks of one operand quad each (operands read kAhead quads
+// early, as f4_mfma_ahead), with a slice of the wave's staging work for later steps issued
+// inside every chunk: work(integral_constant<q>) emits chunk q's slice and Pipe says what it
+// consists of, so each chunk's instructions can be laid out MFMA, VALU..., MFMA, VALU... --
+// one v_mfma_f32_16x16x4f32 holds the pipe for 32 cycles, in which the wave issues the
+// slice.  The accumulation order is f4_mfma's: position 4q+e takes its step's product in
+// chunk q, one MFMA per step.  Chunks are separate scheduling regions (sched_barrier), so
+// no MFMA moves past the end of the step: the caller's wait and s_barrier follow the last
+// fence (profiles/KERNELS.md "Round 11", the scheduling finding).
+//   Pipe::valu(q)    VALU instructions offered a place after each of chunk q's MFMAs
+//   Pipe::ds_read(q) staging LDS reads of chunk q, dealt over its four MFMAs
+//   Pipe::ds_write(q), Pipe::vmem(q)  LDS writes / buffer loads, after the chunk's last MFMA
+template <typename Pipe, int kAhead, int Q, typename Work>
+__device__ __forceinline__ void f4_pipe_chunk(floatx4 (&acc)[kP], floatx4 (&a)[kP / 4],
+                                              floatx4 (&b)[kP / 4], const floatx4* ua,
+                                              const floatx4* vb, Work& work) {
+  constexpr int kQ = kP / 4;
+  if constexpr (Q + kAhead < kQ) {
+    a[Q + kAhead] = ua[Q + kAhead];
+    b[Q + kAhead] = vb[Q + kAhead];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    acc[4 * Q + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[Q][e], b[Q][e], acc[4 * Q + e], 0, 0, 0);
+  work(std::integral_constant<int, Q>{});
+  constexpr int kValu = Pipe::valu(Q), kRead = Pipe::ds_read(Q), kWrite = Pipe::ds_write(Q),
+                kVmem = Pipe::vmem(Q);
+  if constexpr (Q + kAhead < kQ) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  if constexpr (kValu > 0) __builtin_amdgcn_sched_group_barrier(0x002, kValu, 0);
+  if constexpr (kRead > 0) __builtin_amdgcn_sched_group_barrier(0x100, (kRead + 3) / 4, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  if constexpr (kValu > 0) __builtin_amdgcn_sched_group_barrier(0x002, kValu, 0);
+  if constexpr (kRead > 1) __builtin_amdgcn_sched_group_barrier(0x100, (kRead + 2) / 4, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  if constexpr (kValu > 0) __builtin_amdgcn_sched_group_barrier(0x002, kValu, 0);
+  if constexpr (kRead > 2) __builtin_amdgcn_sched_group_barrier(0x100, (kRead + 1) / 4, 0);
+  __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+  if constexpr (kValu > 0) __builtin_amdgcn_sched_group_barrier(0x002, kValu, 0);
+  if constexpr (kRead > 3) __builtin_amdgcn_sched_group_barrier(0x100, kRead / 4, 0);
+  if constexpr (kVmem > 0) __builtin_amdgcn_sched_group_barrier(0x020, kVmem, 0);
+  if constexpr (kWrite > 0) __builtin_amdgcn_sched_group_barrier(0x200, kWrite, 0);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+template <typename Cfg, typename Pipe, int kAhead, typename Work>
+__device__ __forceinline__ void f4_pipe_step(floatx4 (&acc)[kP], const float* buf, int lane,
+                                             int wo, int wt, Work& work) {
+  const floatx4* ua =
+      reinterpret_cast<const floatx4*>(buf + ((wo * kC + (lane >> 4)) * 16 + (lane & 15)) * kP);
+  const floatx4* vb = reinterpret_cast<const floatx4*>(
+      buf + Cfg::kUImg + ((lane >> 4) * kT + wt * 16 + (lane & 15)) * kP);
+  floatx4 a[kP / 4], b[kP / 4];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int q = 0; q < kAhead; ++q) {
+    a[q] = ua[q];
+    b[q] = vb[q];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  f4_pipe_chunk<Pipe, kAhead, 0>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 1>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 2>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 3>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 4>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 5>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 6>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 7>(acc, a, b, ua, vb, work);
+  f4_pipe_chunk<Pipe, kAhead, 8>(acc, a, b, ua, vb, work);
+}
+
+// The x patch waves' slices (waves 0-1 of f4_wgrad_rows_kernel<1>): chunks 0-2 the column passes of B^T d B on the
+// patch of the next step, 3-5 its row passes with the three V stores each completes, 6-8 the
+// ring reads (two rows: the two halo dwords as one ds_read2_b32, the centre 16 bytes) of the
+// step after into the same registers, dead by then.
+struct F4PipePatch {
+  static constexpr int valu(int q) { return q < 6 ? 7 : 0; }
+  static constexpr int ds_read(int q) { return q >= 6 ? 4 : 0; }
+  static constexpr int ds_write(int q) { return q >= 3 && q < 6 ? 3 : 0; }
+  static constexpr int vmem(int) { return 0; }
+};
+
+// Rows 2ip, 2ip+1 of the transformed patch: float4 3ip .. 3ip+2 of the lane's V image.
+__device__ __forceinline__ void f4_store_row_pair(const float* d, float* vdst, int ip) {
+#pragma unroll
+  for (int k = 3 * ip; k < 3 * ip + 3; ++k)
+    reinterpret_cast<floatx4*>(vdst)[k] = floatx4{d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
+}
+
+// Row i of a patch from the lane's chunks of a staged row (r = its left-halo chunk).
+__device__ __forceinline__ void f4_read_ring_row(float* d, const float* r, int i) {
+  d[i * 6 + 0] = r[3];
+  const floatx4 mid = *reinterpret_cast<const floatx4*>(r + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) d[i * 6 + 1 + j] = mid[j];
+  d[i * 6 + 5] = r[8];
 }
 
 // Tap offsets of the 6x6 input patch of output tile t, channel c of the first step.
@@ -1208,8 +1317,7 @@ __device__ __forceinline__ void f4_load_dy(float (&g)[16], __amdgpu_buffer_rsrc_
 
 // M' = A g A^T (36 values, row-major 6x6) of one 4x4 gradient tile (both passes on pairs,
 // packed fp32 VALU, like f4_transform).
-__device__ __forceinline__ void f4_dy_transform(const float (&g)[16], float (&m)[kP]) {
-  float t[6][4];
+__device__ __forceinline__ void f4_dy_transform_cols(const float (&g)[16], float (&t)[6][4]) {
 #pragma unroll
   for (int jp = 0; jp < 2; ++jp) {
     floatx2 col[6];
@@ -1223,17 +1331,26 @@ __device__ __forceinline__ void f4_dy_transform(const float (&g)[16], float (&m)
       t[i][2 * jp + 1] = col[i][1];
     }
   }
+}
+
+// Rows 2ip, 2ip+1 of M' from the column pass's t.
+__device__ __forceinline__ void f4_dy_transform_rows(const float (&t)[6][4], float (&m)[kP],
+                                                     int ip) {
+  floatx2 row[6];
+  a6(floatx2{t[2 * ip][0], t[2 * ip + 1][0]}, floatx2{t[2 * ip][1], t[2 * ip + 1][1]},
+     floatx2{t[2 * ip][2], t[2 * ip + 1][2]}, floatx2{t[2 * ip][3], t[2 * ip + 1][3]}, row);
 #pragma unroll
-  for (int ip = 0; ip < 3; ++ip) {
-    floatx2 row[6];
-    a6(floatx2{t[2 * ip][0], t[2 * ip + 1][0]}, floatx2{t[2 * ip][1], t[2 * ip + 1][1]},
-       floatx2{t[2 * ip][2], t[2 * ip + 1][2]}, floatx2{t[2 * ip][3], t[2 * ip + 1][3]}, row);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      m[2 * ip * 6 + j] = row[j][0];
-      m[(2 * ip + 1) * 6 + j] = row[j][1];
-    }
+  for (int j = 0; j < 6; ++j) {
+    m[2 * ip * 6 + j] = row[j][0];
+    m[(2 * ip + 1) * 6 + j] = row[j][1];
   }
+}
+
+__device__ __forceinline__ void f4_dy_transform(const float (&g)[16], float (&m)[kP]) {
+  float t[6][4];
+  f4_dy_transform_cols(g, t);
+#pragma unroll
+  for (int ip = 0; ip < 3; ++ip) f4_dy_transform_rows(t, m, ip);
 }
 
 // M' into the lane's 36 contiguous LDS floats.
@@ -1540,6 +1657,17 @@ __device__ __forceinline__ F4TileCursor f4_cursor_at(int t, int TH, int TW) {
   return cur;
 }
 
+// The gradient waves' slices of a pipelined step (kStep = 1): chunk 0 both column passes of
+// A g A^T, chunk 1 the next tile's four 16-byte loads (g is dead after chunk 0) and the first
+// row pass, chunks 2-3 the other two; each row pass completes three M' stores.
+struct F4PipeDy {
+  static constexpr int valu(int q) { return q == 0 ? 6 : q < 4 ? 5 : 0; }
+  static constexpr int ds_read(int) { return 0; }
+  static constexpr int ds_write(int q) { return q >= 1 && q < 4 ? 3 : 0; }
+  static constexpr int vmem(int q) { return q == 1 ? 4 : 0; }
+};
+
+template <int kStep = 0>
 __global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_rows_kernel(
     const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dw, int N,
     int C, int K, int H, int W, int TH, int TW, int P, int cblocks, int kblocks, int splits,
@@ -1595,25 +1723,52 @@ __global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_rows_kernel(
     __syncthreads();
     // first tile of the step whose rows are read next (s + 2)
     F4TileCursor rc = f4_cursor_at(4 * (s_begin + 2), TH, TW);
-    for (int s = s_begin; s < s_end; ++s) {
-      const int buf = (s - s_begin) & 1;
-      f4_transform_store(p, vmine + (buf ^ 1) * kBuf);
-      __builtin_amdgcn_sched_barrier(0);
-      // step s+2's rows (past the split's end: staged, never read); a tile behind the row
-      // break sits two chunks further on
-      const float* r = rmine + buf * kWgSlot + (j >= TW - rc.tx ? 8 : 0);
+    if constexpr (kStep == 1) {
+      float* vdst = vmine;
+      const float* r = rmine;
+      auto work = [&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        if constexpr (q < 3) {
+          f4_transform_cols(p.d, q);
+        } else if constexpr (q < 6) {
+          f4_transform_rows(p.d, q - 3);
+          f4_store_row_pair(p.d, vdst, q - 3);
+        } else {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        p.d[i * 6 + 0] = r[i * kWgRS * 4 + 3];
-        const floatx4 mid = *reinterpret_cast<const floatx4*>(r + i * kWgRS * 4 + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) p.d[i * 6 + 1 + e] = mid[e];
-        p.d[i * 6 + 5] = r[i * kWgRS * 4 + 8];
+          for (int i = 2 * (q - 6); i < 2 * (q - 6) + 2; ++i)
+            f4_read_ring_row(p.d, r + i * kWgRS * 4, i);
+        }
+      };
+      for (int s = s_begin; s < s_end; ++s) {
+        const int buf = (s - s_begin) & 1;
+        vdst = vmine + (buf ^ 1) * kBuf;
+        r = rmine + buf * kWgSlot + (j >= TW - rc.tx ? 8 : 0);
+        f4_cursor_advance(rc, TH, TW);
+        f4_pipe_step<Cfg, F4PipePatch, 2>(acc, lds + buf * kBuf, lane, wo, wt, work);
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
       }
-      f4_cursor_advance(rc, TH, TW);
-      __builtin_amdgcn_sched_barrier(0);
-      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
-      __syncthreads();
+    } else {
+      for (int s = s_begin; s < s_end; ++s) {
+        const int buf = (s - s_begin) & 1;
+        f4_transform_store(p, vmine + (buf ^ 1) * kBuf);
+        __builtin_amdgcn_sched_barrier(0);
+        // step s+2's rows (past the split's end: staged, never read); a tile behind the row
+        // break sits two chunks further on
+        const float* r = rmine + buf * kWgSlot + (j >= TW - rc.tx ? 8 : 0);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          p.d[i * 6 + 0] = r[i * kWgRS * 4 + 3];
+          const floatx4 mid = *reinterpret_cast<const floatx4*>(r + i * kWgRS * 4 + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) p.d[i * 6 + 1 + e] = mid[e];
+          p.d[i * 6 + 5] = r[i * kWgRS * 4 + 8];
+        }
+        f4_cursor_advance(rc, TH, TW);
+        __builtin_amdgcn_sched_barrier(0);
+        f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+        __syncthreads();
+      }
     }
   } else if (dy_wave) {
     // -- gradient tiles: channel k0 + 16*d + (lane & 15), tile (lane >> 4) of the step --
@@ -1630,15 +1785,38 @@ __global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_rows_kernel(
     __syncthreads();
     f4_cursor_advance(cur, TH, TW);
     f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
-    for (int s = s_begin; s < s_end; ++s) {
-      const int buf = (s - s_begin) & 1;
-      f4_dy_transform_store(g, mmine + (buf ^ 1) * kBuf);
-      __builtin_amdgcn_sched_barrier(0);
-      f4_cursor_advance(cur, TH, TW);
-      f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
-      __builtin_amdgcn_sched_barrier(0);
-      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
-      __syncthreads();
+    if constexpr (kStep == 1) {
+      float* mdst = mmine;
+      float t[6][4], m[kP];
+      auto work = [&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        if constexpr (q == 0) {
+          f4_dy_transform_cols(g, t);
+        } else if constexpr (q < 4) {
+          if constexpr (q == 1) f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
+          f4_dy_transform_rows(t, m, q - 1);
+          f4_store_row_pair(m, mdst, q - 1);
+        }
+      };
+      for (int s = s_begin; s < s_end; ++s) {
+        const int buf = (s - s_begin) & 1;
+        mdst = mmine + (buf ^ 1) * kBuf;
+        f4_cursor_advance(cur, TH, TW);
+        f4_pipe_step<Cfg, F4PipeDy, 2>(acc, lds + buf * kBuf, lane, wo, wt, work);
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      for (int s = s_begin; s < s_end; ++s) {
+        const int buf = (s - s_begin) & 1;
+        f4_dy_transform_store(g, mmine + (buf ^ 1) * kBuf);
+        __builtin_amdgcn_sched_barrier(0);
+        f4_cursor_advance(cur, TH, TW);
+        f4_load_dy<true>(g, dyr, cur, k, N, K, H, W);
+        __builtin_amdgcn_sched_barrier(0);
+        f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+        __syncthreads();
+      }
     }
   } else {
     // -- staging waves: lane = (chunk q of a row, channel cl of 16); 12 chunks per lane:
@@ -1690,7 +1868,11 @@ __global__ __launch_bounds__(kWgThreads, 1) void f4_wgrad_rows_kernel(
       f4_cursor_advance(sc, TH, TW);  // step s + 3
       load_rows(sc);
       __builtin_amdgcn_sched_barrier(0);
-      f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      if constexpr (kStep == 1) {
+        f4_mfma_ahead<Cfg, 2>(acc, lds + buf * kBuf, lane, wo, wt);
+      } else {
+        f4_mfma<Cfg>(acc, lds + buf * kBuf, lane, wo, wt);
+      }
       __builtin_amdgcn_sched_barrier(0);
       store_rows(raw + (buf ^ 1) * kWgSlot);
       __syncthreads();
@@ -3038,6 +3220,10 @@ constexpr F4Variant kF4Variants[] = {
     {21, 4, f4_conv_rows_kernel<46, 3, 4, 1>, nullptr, nullptr, 24, 6},
     {22, 4, f4_conv_rows_kernel<46, 3, 4, 7>, nullptr, nullptr, 24, 6},
     {24, 4, f4_conv_emu_kernel<false>, f4_conv_emu_kernel<true>, nullptr, 0, 0, kEC},
+    // 16's kernels under a second id: the A/B arm of a new step body.  The pipelined step
+    // (f4_pipe_step) measured 2-4 % slower than this one on both instances, so 16 keeps it
+    // (profiles/KERNELS.md "Round 19")
+    {25, 4, f4_conv_rows_kernel<46, 3>, nullptr, f4_conv_rows_kernel<66, 5>, 8, 6},
 };
 // Modelled time of one 16-channel chunk of a variant-24 workgroup for split_k_by_cost,
 // fitted to benchmarks/split_sweep.py --ops emu (profiles/r11/f4_emu/split_sweep_emu.json):
@@ -3475,9 +3661,9 @@ bool wino4_wgrad_supported(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w
 WinoPlan wino4_wgrad_plan(int64_t n, int64_t c, int64_t k, int64_t h, int64_t w, int variant,
                           int splits) {
   WinoPlan plan;
-  plan.variant = variant >= 1 && variant <= 3 ? variant : 0;
+  plan.variant = variant >= 1 && variant <= 4 ? variant : 0;
   // the row-staged x operand: whole 16-byte chunks, at most one row break per step
-  if (plan.variant == 3 && ((w & 3) != 0 || w < 16)) plan.variant = 0;
+  if ((plan.variant == 3 || plan.variant == 4) && ((w & 3) != 0 || w < 16)) plan.variant = 0;
   const int64_t tiles = n * ((h + 3) / 4) * ((w + 3) / 4);
   const int64_t cpad = (c + 31) / 32 * 32, kpad = (k + 63) / 64 * 64;  // 32 c x 64 k blocks
   const bool emu = plan.variant == 2;
@@ -3542,7 +3728,8 @@ void launch_wino4_wgrad(const float* x, const float* dy, float* dw, float* ws, i
                        accum && splits == 1);
   } else {
     auto kernel = (w & 3) == 0 ? f4_wgrad_kernel<true> : f4_wgrad_kernel<false>;
-    if (plan.variant == 3) kernel = f4_wgrad_rows_kernel;
+    if (plan.variant == 3) kernel = f4_wgrad_rows_kernel<1>;
+    if (plan.variant == 4) kernel = f4_wgrad_rows_kernel<0>;
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nwg)), dim3(kWgThreads), 0,
                        stream, x, dy, splits > 1 ? partial : dw, static_cast<int>(n),
                        static_cast<int>(c), static_cast<int>(k), static_cast<int>(h),
