@@ -2029,6 +2029,91 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attention_backward(
   return {dq, dk, dv};
 }
 
+// ---- LayerNorm / RMSNorm over the last dimension (layernorm.hip) ------------------------------
+// x, y, dy, dx [..., N] flattened into R rows; weight, bias [N]; mean, rstd one per row.
+
+constexpr int64_t kLayerNormMaxWidth = 8192;
+
+std::vector<int64_t> without_last(const at::Tensor& t) {
+  return std::vector<int64_t>(t.sizes().begin(), t.sizes().end() - 1);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> layernorm_forward(
+    const at::Tensor& x, const c10::optional<at::Tensor>& weight,
+    const c10::optional<at::Tensor>& bias, double eps, bool rms) {
+  check_f32(x, "x", x);
+  const int R = linear_rows(x, "x");
+  const int64_t N = x.size(-1);
+  TORCH_CHECK(N <= kLayerNormMaxWidth, "layernorm_forward: rows of at most ",
+              kLayerNormMaxWidth, " elements");
+  const float* w = opt_ptr(weight, "weight", x, N);
+  const float* b = opt_ptr(bias, "bias", x, N);
+  TORCH_CHECK(b == nullptr || (w != nullptr && !rms),
+              "layernorm_forward: a bias needs a weight, and RMSNorm has none");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty_like(x);
+  auto rstd = at::empty(without_last(x), x.options());
+  auto mean = rms ? at::empty({0}, x.options()) : at::empty_like(rstd);
+  launch_layernorm_forward(x.data_ptr<float>(), w, b, y.data_ptr<float>(),
+                           rms ? nullptr : mean.data_ptr<float>(), rstd.data_ptr<float>(), R,
+                           static_cast<int>(N), static_cast<float>(eps), rms, cur_stream(x));
+  return {y, mean, rstd};
+}
+
+// dweight / dbias: a fresh tensor, or the given `into` -- stored, or with `accumulate` added
+// to (the .grad of the gradacc protocol).  need_dweight / need_dbias = false leave them
+// undefined; without a weight, or with neither wanted, the partials and their reduction are
+// skipped.  dx is undefined unless need_dx.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> layernorm_backward(
+    const at::Tensor& dy, const at::Tensor& x, const at::Tensor& mean, const at::Tensor& rstd,
+    const c10::optional<at::Tensor>& weight, const c10::optional<at::Tensor>& dweight_into,
+    const c10::optional<at::Tensor>& dbias_into, bool accumulate, bool need_dx, bool rms,
+    bool need_dweight, bool need_dbias) {
+  check_f32(dy, "dy", dy);
+  check_f32(x, "x", dy);
+  check_f32(rstd, "rstd", dy);
+  const int R = linear_rows(x, "x");
+  const int64_t N = x.size(-1);
+  TORCH_CHECK(dy.sizes() == x.sizes(), "layernorm_backward: dy and x differ in shape");
+  TORCH_CHECK(N <= kLayerNormMaxWidth, "layernorm_backward: rows of at most ",
+              kLayerNormMaxWidth, " elements");
+  TORCH_CHECK(rstd.numel() == R, "layernorm_backward: rstd must have one element per row");
+  if (!rms) {
+    check_f32(mean, "mean", dy);
+    TORCH_CHECK(mean.numel() == R, "layernorm_backward: mean must have one element per row");
+  }
+  const float* w = opt_ptr(weight, "weight", dy, N);
+  need_dweight = need_dweight && w != nullptr;
+  need_dbias = need_dbias && w != nullptr && !rms;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  at::Tensor dx, dw, db, part;
+  if (need_dx) dx = at::empty_like(x);
+  bool acc_dw = false, acc_db = false;
+  auto grad_out = [&](const c10::optional<at::Tensor>& into, const char* name, bool& acc) {
+    const bool given = into.has_value() && into->defined();
+    at::Tensor g = given ? *into : at::empty({N}, dy.options());
+    check_f32(g, name, dy);
+    TORCH_CHECK(g.numel() == N, "layernorm_backward: `", name, "` must have N elements");
+    acc = given && accumulate;
+    return g;
+  };
+  if (need_dweight) dw = grad_out(dweight_into, "dweight_into", acc_dw);
+  if (need_dbias) db = grad_out(dbias_into, "dbias_into", acc_db);
+  const bool partials = need_dweight || need_dbias;
+  if (!partials && !need_dx) return {dx, dw, db};
+  const LayerNormPlan plan = layernorm_plan(R, static_cast<int>(N));  // decided once
+  if (partials)  // from the caching allocator, on the current stream
+    part = at::empty({plan.grid, rms ? 1 : 2, N}, dy.options());
+  launch_layernorm_backward(dy.data_ptr<float>(), x.data_ptr<float>(),
+                            rms ? nullptr : mean.data_ptr<float>(), rstd.data_ptr<float>(), w,
+                            need_dx ? dx.data_ptr<float>() : nullptr,
+                            partials ? part.data_ptr<float>() : nullptr,
+                            need_dweight ? dw.data_ptr<float>() : nullptr,
+                            need_dbias ? db.data_ptr<float>() : nullptr, acc_dw, acc_db, R,
+                            static_cast<int>(N), rms, plan, cur_stream(dy));
+  return {dx, dw, db};
+}
+
 }  // namespace
 }  // namespace tgpipe
 
@@ -2105,6 +2190,21 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
         "(Tensor, Tensor)");
   m.def("attention_backward(Tensor do, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, "
         "bool causal, float scale) -> (Tensor, Tensor, Tensor)");
+  m.def("layernorm_forward(Tensor x, Tensor? weight, Tensor? bias, float eps, bool rms) -> "
+        "(Tensor y, Tensor mean, Tensor rstd)");
+  m.def("layernorm_backward(Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor? weight, "
+        "Tensor? dweight_into, Tensor? dbias_into, bool accumulate, bool need_dx, "
+        "bool rms, bool need_dweight=True, bool need_dbias=True) -> "
+        "(Tensor dx, Tensor dweight, Tensor dbias)");
+  // test / profiling hooks, not part of the public ops
+  m.def("_layernorm_force_instance(int wide) -> ()", [](int64_t wide) {
+    tgpipe::layernorm_force_instance(static_cast<int>(wide));
+  });
+  // [widest row of the wave-per-row instance, rows one sweep of the backward grid covers at n]
+  m.def("_layernorm_limits(int n) -> int[]", [](int64_t n) {
+    return std::vector<int64_t>{tgpipe::layernorm_wave_row_max(),
+                                tgpipe::layernorm_backward_sweep(static_cast<int>(n))};
+  });
 }
 
 TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
@@ -2126,6 +2226,8 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("linear_bias_grad", &tgpipe::linear_bias_grad);
   m.impl("attention_forward", &tgpipe::attention_forward);
   m.impl("attention_backward", &tgpipe::attention_backward);
+  m.impl("layernorm_forward", &tgpipe::layernorm_forward);
+  m.impl("layernorm_backward", &tgpipe::layernorm_backward);
   m.impl("bn_train_forward", &tgpipe::bn_train_forward);
   m.impl("bn_train_backward", &tgpipe::bn_train_backward);
   m.impl("dbn_commit64", &tgpipe::dbn_commit64);

@@ -424,6 +424,34 @@ void launch_attention_forward(const AttnArgs& args, bool causal, hipStream_t str
 // dV and dK kernels at D = 128), then dQ (a workgroup per query block)
 void launch_attention_backward(const AttnArgs& args, bool causal, hipStream_t stream);
 
+// LayerNorm / RMSNorm (`rms`: no mean, no bias) over the last dimension of contiguous fp32
+// rows x[R][N], 1 <= N <= 8192, R >= 1, every tensor below 2 GiB (layernorm.hip).  w, b:
+// [N] or null.  Forward writes y, rstd[R] and, unless rms, mean[R].
+void launch_layernorm_forward(const float* x, const float* w, const float* b, float* y,
+                              float* mean, float* rstd, int R, int N, float eps, bool rms,
+                              hipStream_t stream);
+// The backward's launch, decided once per call (the caller sizes `part` from it and hands the
+// same plan to the launcher).
+struct LayerNormPlan {
+  bool wide;  // the workgroup-per-row instance
+  int grid;   // workgroups of the persistent backward = partials written
+};
+LayerNormPlan layernorm_plan(int R, int N);
+// One persistent pass over dy and x: dx (null: not wanted) and, with `part` (floats:
+// plan.grid * (rms ? 1 : 2) * N), the per-workgroup partials of dw = sum_r dy * xhat and
+// db = sum_r dy, which a second launch sums in a fixed order into dw / db (either may be null;
+// accumulate_*: add to what is there).  No atomics.
+void launch_layernorm_backward(const float* dy, const float* x, const float* mean,
+                               const float* rstd, const float* w, float* dx, float* part,
+                               float* dw, float* db, bool accumulate_dw, bool accumulate_db,
+                               int R, int N, bool rms, const LayerNormPlan& plan,
+                               hipStream_t stream);
+int layernorm_backward_sweep(int N);  // rows one sweep of the full backward grid covers
+int layernorm_wave_row_max();         // widest row of the wave-per-row instance
+// Test / profiling hook: 0 = the wave-per-row instance wherever it has the registers
+// (N <= 2048), 1 = the workgroup-per-row instance everywhere, -1 = the host rule.
+void layernorm_force_instance(int wide);
+
 // (mean, M2) partials of z[n][c][s] per (image, channel): part_*[n][c] (width s).
 void launch_bn_stats(const float* z, float* part_mean, float* part_m2, int64_t n, int64_t c,
                      int64_t s, hipStream_t stream);

@@ -9,6 +9,7 @@ from torch import Tensor, nn
 import torch
 
 from torchgpipe_amd.ops.attention import NativeSelfAttention
+from torchgpipe_amd.ops.layernorm import NativeLayerNorm
 from torchgpipe_amd.ops.linear import NativeLinear
 
 __all__ = ['transformer_lm']
@@ -30,9 +31,10 @@ class Embedding(nn.Module):
 class AttentionBlock(nn.Module):
     """``x + attention(norm(x))``, causal."""
 
-    def __init__(self, d_model: int, heads: int, native_linear: bool) -> None:
+    def __init__(self, d_model: int, heads: int, native_linear: bool,
+                 native_norm: bool = False) -> None:
         super().__init__()
-        self.norm = nn.LayerNorm(d_model)
+        self.norm = (NativeLayerNorm if native_norm else nn.LayerNorm)(d_model)
         self.attn = NativeSelfAttention(d_model, heads, causal=True,
                                         native_linear=native_linear)
 
@@ -43,10 +45,10 @@ class AttentionBlock(nn.Module):
 class MLPBlock(nn.Module):
     """``x + fc2(gelu(fc1(norm(x))))`` with a hidden width of ``4 * d_model``."""
 
-    def __init__(self, d_model: int, native_linear: bool) -> None:
+    def __init__(self, d_model: int, native_linear: bool, native_norm: bool = False) -> None:
         super().__init__()
         linear = NativeLinear if native_linear else nn.Linear
-        self.norm = nn.LayerNorm(d_model)
+        self.norm = (NativeLayerNorm if native_norm else nn.LayerNorm)(d_model)
         self.fc1 = linear(d_model, 4 * d_model)
         self.act = nn.GELU()
         self.fc2 = linear(4 * d_model, d_model)
@@ -58,9 +60,10 @@ class MLPBlock(nn.Module):
 class Head(nn.Module):
     """Final LayerNorm and the vocabulary projection: ``[B, T, d_model]`` -> ``[B, T, vocab]``."""
 
-    def __init__(self, d_model: int, vocab: int, native_linear: bool) -> None:
+    def __init__(self, d_model: int, vocab: int, native_linear: bool,
+                 native_norm: bool = False) -> None:
         super().__init__()
-        self.norm = nn.LayerNorm(d_model)
+        self.norm = (NativeLayerNorm if native_norm else nn.LayerNorm)(d_model)
         self.out = (NativeLinear if native_linear else nn.Linear)(d_model, vocab, bias=False)
 
     def forward(self, x: Tensor) -> Tensor:
@@ -68,15 +71,17 @@ class Head(nn.Module):
 
 
 def transformer_lm(vocab: int = 32000, d_model: int = 768, heads: int = 12, layers: int = 12,
-                   seq_len: int = 1024, native_linear: bool = False) -> nn.Sequential:
+                   seq_len: int = 1024, native_linear: bool = False,
+                   native_norm: bool = False) -> nn.Sequential:
     """Embedding, ``layers`` x (attention block, MLP block), head: ``2 * layers + 2`` children
     mapping int64 ``tokens [B, T <= seq_len]`` to logits ``[B, T, vocab]``.
 
     ``d_model == 64 * heads`` or ``128 * heads`` puts the attention on the native kernels;
-    ``native_linear`` builds every projection from ``ops.linear.NativeLinear``."""
+    ``native_linear`` builds every projection from ``ops.linear.NativeLinear``, ``native_norm``
+    every LayerNorm from ``ops.layernorm.NativeLayerNorm``."""
     blocks = [Embedding(vocab, d_model, seq_len)]
     for _ in range(layers):
-        blocks.append(AttentionBlock(d_model, heads, native_linear))
-        blocks.append(MLPBlock(d_model, native_linear))
-    blocks.append(Head(d_model, vocab, native_linear))
+        blocks.append(AttentionBlock(d_model, heads, native_linear, native_norm))
+        blocks.append(MLPBlock(d_model, native_linear, native_norm))
+    blocks.append(Head(d_model, vocab, native_linear, native_norm))
     return nn.Sequential(*blocks)

@@ -9,9 +9,14 @@
 * :mod:`.linear` — ``nn.Linear`` on the split-bf16 dense GEMM (``NativeLinear``, opt-in)
 * :mod:`.attention` — fused fp32 attention, head dims 64 / 128, split-bf16
   (``NativeSelfAttention``)
+* :mod:`.layernorm` — ``nn.LayerNorm`` / ``nn.RMSNorm`` over the last dimension, rows in
+  registers, fixed-order affine gradients (``NativeLayerNorm``, ``NativeRMSNorm``, opt-in)
 """
-from torchgpipe_amd.ops import _ext, gradclip, linear
+from torchgpipe_amd.ops import _ext, gradclip, layernorm, linear
+from torchgpipe_amd.ops.layernorm import (NativeLayerNorm, NativeRMSNorm, native_layer_norm,
+                                          native_rms_norm)
 
 available = _ext.available
 
-__all__ = ['available', 'gradclip', 'linear']
+__all__ = ['available', 'gradclip', 'layernorm', 'linear', 'NativeLayerNorm', 'NativeRMSNorm',
+           'native_layer_norm', 'native_rms_norm']
