@@ -29,7 +29,7 @@ ROCM = os.environ.get('ROCM_PATH', '/opt/rocm')
 KERNEL_SOURCES = ['kernels.hip', 'winograd.hip', 'winograd_f4.hip', 'conv_gemm.hip',
                   'batchnorm.hip', 'pool.hip', 'unet_ops.hip', 'gradclip.hip', 'wire.hip',
                   'optim.hip', 'linear.hip', 'attention.hip', 'attention128.hip',
-                  'layernorm.hip']
+                  'layernorm.hip', 'cross_entropy.hip']
 # extra hipcc flags per kernel source.  linear.hip: no packed-f32 VALU forms (v_pk_*_f32) for
 # its float4 epilogue adds -- plain f32 adds, rounded as the scalar path rounds them;
 # attention.hip, attention128.hip: the same for their softmax and rescale arithmetic

@@ -2114,6 +2114,75 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> layernorm_backward(
   return {dx, dw, db};
 }
 
+// ---- Softmax cross-entropy over logit rows (cross_entropy.hip) --------------------------------
+// logits [R][V] fp32, target [R] int64; reduction 0 none, 1 mean, 2 sum (ATen's numbering).
+// Shapes, dtypes and devices are checked here, target values on the device only.
+
+void check_logits(const at::Tensor& logits, const at::Tensor& target, const char* op) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kFloat && logits.is_contiguous() &&
+                  logits.dim() == 2 && logits.numel() > 0,
+              op, ": logits must be a contiguous float32 [R, V] GPU tensor with R, V >= 1");
+  TORCH_CHECK(logits.size(1) * 4 <= kMaxBytes, op, ": a row of logits must stay below 2 GiB");
+  // one workgroup per row and 4096 columns at the most
+  TORCH_CHECK(logits.size(0) * ((logits.size(1) + 4095) / 4096) <= INT32_MAX, op,
+              ": too many rows");
+  TORCH_CHECK(target.device() == logits.device() && target.scalar_type() == at::kLong &&
+                  target.is_contiguous() && target.dim() == 1 &&
+                  target.size(0) == logits.size(0),
+              op, ": target must be a contiguous int64 [R] tensor on ", logits.device());
+}
+
+void check_row_floats(const at::Tensor& t, const char* name, const at::Tensor& logits,
+                      int64_t numel) {
+  TORCH_CHECK(t.device() == logits.device() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == numel,
+              "cross_entropy_backward: ", name, " must be a contiguous float32 tensor of ", numel,
+              " element(s) on ", logits.device());
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> cross_entropy_forward(
+    const at::Tensor& logits, const at::Tensor& target, int64_t ignore_index,
+    double label_smoothing, int64_t reduction) {
+  check_logits(logits, target, "cross_entropy_forward");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0,
+              "cross_entropy_forward: label_smoothing must be in [0, 1)");
+  TORCH_CHECK(reduction >= 0 && reduction <= 2, "cross_entropy_forward: reduction 0, 1 or 2");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  const int64_t R = logits.size(0);
+  auto stat = at::empty({R, 2}, logits.options());  // (row maximum, 1 / sum exp(x - maximum))
+  auto loss_rows = at::empty({R}, logits.options());
+  auto inv_count = at::empty({1}, logits.options());
+  at::Tensor loss = reduction == 0 ? loss_rows : at::empty(at::IntArrayRef{}, logits.options());
+  launch_cross_entropy_forward(logits.data_ptr<float>(), target.data_ptr<int64_t>(),
+                               stat.data_ptr<float>(), loss_rows.data_ptr<float>(),
+                               reduction == 0 ? nullptr : loss.data_ptr<float>(),
+                               inv_count.data_ptr<float>(), static_cast<int>(R),
+                               static_cast<int>(logits.size(1)), ignore_index,
+                               static_cast<float>(label_smoothing), reduction == 1,
+                               cur_stream(logits));
+  return {loss, stat, inv_count};
+}
+
+at::Tensor cross_entropy_backward(const at::Tensor& grad, const at::Tensor& logits,
+                                  const at::Tensor& target, const at::Tensor& stat,
+                                  const at::Tensor& inv_count, int64_t ignore_index,
+                                  double label_smoothing, int64_t reduction) {
+  check_logits(logits, target, "cross_entropy_backward");
+  const int64_t R = logits.size(0);
+  check_row_floats(grad, "grad", logits, reduction == 0 ? R : 1);
+  check_row_floats(stat, "stat", logits, 2 * R);
+  check_row_floats(inv_count, "inv_count", logits, 1);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto dx = at::empty_like(logits);
+  launch_cross_entropy_backward(grad.data_ptr<float>(), inv_count.data_ptr<float>(),
+                                logits.data_ptr<float>(), target.data_ptr<int64_t>(),
+                                stat.data_ptr<float>(), dx.data_ptr<float>(), static_cast<int>(R),
+                                static_cast<int>(logits.size(1)), ignore_index,
+                                static_cast<float>(label_smoothing), reduction == 0,
+                                cur_stream(logits));
+  return dx;
+}
+
 }  // namespace
 }  // namespace tgpipe
 
@@ -2205,6 +2274,23 @@ TORCH_LIBRARY_FRAGMENT(tgpipe, m) {
     return std::vector<int64_t>{tgpipe::layernorm_wave_row_max(),
                                 tgpipe::layernorm_backward_sweep(static_cast<int>(n))};
   });
+  m.def("cross_entropy_forward(Tensor logits, Tensor target, int ignore_index, "
+        "float label_smoothing, int reduction) -> (Tensor loss, Tensor stat, Tensor inv_count)");
+  m.def("cross_entropy_backward(Tensor grad, Tensor logits, Tensor target, Tensor stat, "
+        "Tensor inv_count, int ignore_index, float label_smoothing, int reduction) -> Tensor");
+  // wide: 0 / 1 the wave-per-row / workgroup instances at any width, -1 the host rule;
+  // chunk: 4096 or 8192 columns per workgroup of the wide backward, 0 the default
+  m.def("_cross_entropy_force_instance(int wide, int chunk=0) -> ()",
+        [](int64_t wide, int64_t chunk) {
+          tgpipe::cross_entropy_force_instance(static_cast<int>(wide), static_cast<int>(chunk));
+        });
+  // [widest row of the wave-per-row instances, columns per workgroup of the wide backward on
+  // the float4 path, the same on the dword path]
+  m.def("_cross_entropy_limits() -> int[]", []() {
+    return std::vector<int64_t>{tgpipe::cross_entropy_wave_row_max(),
+                                tgpipe::cross_entropy_backward_chunk(true),
+                                tgpipe::cross_entropy_backward_chunk(false)};
+  });
 }
 
 TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
@@ -2228,6 +2314,8 @@ TORCH_LIBRARY_IMPL(tgpipe, CUDA, m) {
   m.impl("attention_backward", &tgpipe::attention_backward);
   m.impl("layernorm_forward", &tgpipe::layernorm_forward);
   m.impl("layernorm_backward", &tgpipe::layernorm_backward);
+  m.impl("cross_entropy_forward", &tgpipe::cross_entropy_forward);
+  m.impl("cross_entropy_backward", &tgpipe::cross_entropy_backward);
   m.impl("bn_train_forward", &tgpipe::bn_train_forward);
   m.impl("bn_train_backward", &tgpipe::bn_train_backward);
   m.impl("dbn_commit64", &tgpipe::dbn_commit64);

@@ -452,6 +452,32 @@ int layernorm_wave_row_max();         // widest row of the wave-per-row instance
 // (N <= 2048), 1 = the workgroup-per-row instance everywhere, -1 = the host rule.
 void layernorm_force_instance(int wide);
 
+// Softmax cross-entropy over contiguous fp32 logit rows x[R][V] with int64 targets t[R]
+// (cross_entropy.hip); R, V >= 1, a row below 2 GiB, the tensor of any size.  eps: label
+// smoothing in [0, 1).  The forward reads the logits once and writes stat[R][2] (the row's
+// maximum m and 1 / sum exp(x - m): what the backward needs of the softmax) and loss_rows[R]
+// (0 for rows whose target is ignore_index, NaN for any other target outside [0, V)); then
+// one workgroup writes inv_count[0] (1 / rows not ignored with `mean`, else 1) and, unless
+// loss is null, loss[0] = sum loss_rows (over that count with `mean`).
+void launch_cross_entropy_forward(const float* x, const int64_t* target, float* stat,
+                                  float* loss_rows, float* loss, float* inv_count, int R, int V,
+                                  int64_t ignore_index, float eps, bool mean,
+                                  hipStream_t stream);
+// dx = s_r (softmax - (1 - eps) onehot - eps / V), zero for ignored rows; s_r = grad[r] with
+// per_row, else grad[0] * inv_count[0], both read on the device.
+void launch_cross_entropy_backward(const float* grad, const float* inv_count, const float* x,
+                                   const int64_t* target, const float* stat, float* dx, int R,
+                                   int V, int64_t ignore_index, float eps, bool per_row,
+                                   hipStream_t stream);
+int cross_entropy_wave_row_max();  // widest row of the wave-per-row instances
+// columns per workgroup of the wide backward, on the float4 (V % 4 == 0, 16-byte aligned
+// bases) or on the dword path
+int cross_entropy_backward_chunk(bool vec);
+// Test / profiling hook.  wide: 0 = the wave-per-row instances at any width, 1 = the
+// workgroup instances at any width, -1 = the host rule.  chunk_cols: 4096 or 8192 columns
+// per workgroup of the wide backward, anything else = the default.
+void cross_entropy_force_instance(int wide, int chunk_cols);
+
 // (mean, M2) partials of z[n][c][s] per (image, channel): part_*[n][c] (width s).
 void launch_bn_stats(const float* z, float* part_mean, float* part_m2, int64_t n, int64_t c,
                      int64_t s, hipStream_t stream);

@@ -11,12 +11,16 @@
   (``NativeSelfAttention``)
 * :mod:`.layernorm` — ``nn.LayerNorm`` / ``nn.RMSNorm`` over the last dimension, rows in
   registers, fixed-order affine gradients (``NativeLayerNorm``, ``NativeRMSNorm``, opt-in)
+* :mod:`.loss` — softmax cross-entropy over streamed logit rows: one read forward, one read
+  and one write backward, no saved log-softmax (``NativeCrossEntropyLoss``, opt-in)
 """
-from torchgpipe_amd.ops import _ext, gradclip, layernorm, linear
+from torchgpipe_amd.ops import _ext, gradclip, layernorm, linear, loss
 from torchgpipe_amd.ops.layernorm import (NativeLayerNorm, NativeRMSNorm, native_layer_norm,
                                           native_rms_norm)
+from torchgpipe_amd.ops.loss import NativeCrossEntropyLoss, native_cross_entropy
 
 available = _ext.available
 
-__all__ = ['available', 'gradclip', 'layernorm', 'linear', 'NativeLayerNorm', 'NativeRMSNorm',
-           'native_layer_norm', 'native_rms_norm']
+__all__ = ['available', 'gradclip', 'layernorm', 'linear', 'loss', 'NativeLayerNorm',
+           'NativeRMSNorm', 'native_layer_norm', 'native_rms_norm', 'NativeCrossEntropyLoss',
+           'native_cross_entropy']
